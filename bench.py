@@ -12,9 +12,18 @@ the 64-cluster instance sharded over the N GPUs (STRONG scaling, 8 clusters per 
 GPU a C3-sized shard (J = 64 N clusters coupled by n_y = 128); `value` is then that instance's
 iterations/s and `shard_iterations_per_s_summed` = N x value.
 
-Also reported: the Schur-assembly roofline (its kernels timed on the device clock inside the
-timed region), and a CPU baseline: the C++/OpenMP restatement of the reference algorithm
-(oracle/cpu_restatement.cpp) at the bench's word type on the host's cores, rank 0 at N = 1.
+A plain run sets up, warms up, times the --steps loop bodies, writes the iterate of the last
+timed body when --dump-outputs DIR is given, and prints one JSON line.  Its `roofline` is the
+Schur-assembly roofline where the stage was timed on the device clock inside the timed region
+(the synchronous fp64 loop); elsewhere its time fields are null.
+
+With --full also reported, from passes of their own after the timed region: the per-stage phase
+breakdown (instrumented pass, which is also the Schur time where the device-clock stamps do not
+exist), the host cost of enqueueing one loop body eagerly, the counted HBM traffic and issued
+MFMA work of the Schur stage (from the committed counter summaries of this very build), and a
+CPU baseline: the C++/OpenMP restatement of the reference algorithm
+(oracle/cpu_restatement.cpp) at the bench's word type on the host's cores, rank 0 at N = 1
+(--no-cpu leaves it out).
 """
 from __future__ import annotations
 
@@ -151,14 +160,41 @@ def cpu_baseline(pk, cons, b, bi, precision=1, budget_s=15.0):
                        f"(oracle/cpu_restatement.cpp) at {DTYPES[precision]}, {threads} OpenMP threads")}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20   # --dump-outputs: all files together stay below this
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(path, arrays):
+    """Write {name: flat float64 array} as path/<name>.npy.  Arrays whose share of
+    DUMP_LIMIT_BYTES is too small for all their entries are written as a fixed sample: the
+    entries at sorted indices drawn without replacement by a generator seeded with
+    DUMP_SAMPLE_SEED and the array's length (the same indices in every run and every build)."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // (8 * len(arrays))   # entries per array
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > share:
+            rng = np.random.default_rng([DUMP_SAMPLE_SEED, a.size])
+            a = a[np.sort(rng.choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed loop bodies (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beside the headline figure: the instrumented phase "
+                         "breakdown, the eager host-enqueue cost, the counter-based Schur traffic "
+                         "and the CPU baseline (see --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the iterate the last timed loop body "
+                         "returned (x, X, y, Y in the C-ABI's flat layout; the leading fp64 word "
+                         "at double-double / quad-double) and its log row (stats) as DIR/<name>.npy")
     ap.add_argument("--config", default="c3")
     ap.add_argument("--precision", type=int, default=1)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--loop", choices=["auto", "sync", "pipelined"], default="auto",
                     help="host loop: wait for every loop body (sync; hipGraph replay, faster at one "
@@ -171,6 +207,8 @@ def main():
                          "configs[2], the default), weak = one config-sized shard per GPU (J x N "
                          "clusters)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -242,26 +280,39 @@ def main():
     # restarts per cause (period / mu floor), reported in the JSON for the timed window
     restarts = {"period": 0, "mu_floor": 0}
 
-    def maybe_restart():
+    held = [None]   # cause of a restart that is due but held back (run_bodies(hold_last=True))
+
+    def restart(cause):
+        restarts[cause] += 1
+        dev.restore_state()
+        feas[0] = False   # the snapshot is the (infeasible) initial point
+        last_mu[0] = 1.0
+
+    def maybe_restart(hold=False):
         count[0] += 1
         if count[0] % RESTART == 0 or last_mu[0] < MU_FLOOR:
-            restarts["period" if count[0] % RESTART == 0 else "mu_floor"] += 1
-            dev.restore_state()
-            feas[0] = False   # the snapshot is the (infeasible) initial point
-            last_mu[0] = 1.0
+            cause = "period" if count[0] % RESTART == 0 else "mu_floor"
+            if hold:
+                held[0] = cause
+            else:
+                restart(cause)
 
-    def run_bodies(n):
+    def run_bodies(n, hold_last=False):
         """n loop bodies as solverank1sdp runs them: the host one body behind the device
-        (clrsdp_iterate_async / _wait), every log row read back."""
+        (clrsdp_iterate_async / _wait), every log row read back.  Returns the last body's log
+        row.  With hold_last a restart that falls due after the last body is not carried out
+        (it prepares the next body and would overwrite the iterate this one returned): the
+        caller does it with restart(held[0]) once it has read the state."""
+        st = None
         if not pipelined:
-            for _ in range(n):
-                step()
-                maybe_restart()
-            return
+            for i in range(n):
+                st = step()
+                maybe_restart(hold_last and i == n - 1)
+            return st
         inflight = 0
-        for _ in range(n):
+        for i in range(n):
             dev.iterate_async(prm)
-            maybe_restart()
+            maybe_restart(hold_last and i == n - 1)
             inflight += 1
             if inflight == 2:
                 st, ran = dev.iterate_wait()
@@ -270,10 +321,11 @@ def main():
                     raise RuntimeError("solver terminated inside the benchmark window")
                 last_mu[0] = st.mu   # (one body behind: the MU_FLOOR restart comes a body later)
         while inflight:
-            _, ran = dev.iterate_wait()
+            st, ran = dev.iterate_wait()
             inflight -= 1
             if not ran:
                 raise RuntimeError("solver terminated inside the benchmark window")
+        return st
 
     dev.save_state()   # snapshot of the initial point (restart target of long windows)
     run_bodies(args.warmup)
@@ -301,53 +353,69 @@ def main():
     barrier_sync()
     restarts.update(period=0, mu_floor=0)
     t0 = time.perf_counter()
-    run_bodies(args.steps)
+    last = run_bodies(args.steps, hold_last=True)
     barrier_sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the iterate (at N > 1
+        # rank 0's view of it, as clrsdp_get_state returns it) and the body's log row
+        from clrsdp_amd.instance import blocks_to_flat
+        xo, Xo, yo, Yo = dev.get_state()
+        dump_outputs(args.dump_outputs, {
+            "x": xo, "X": blocks_to_flat(Xo), "y": yo, "Y": blocks_to_flat(Yo),
+            "stats": [last.mu, last.P_err, last.p_err, last.d_err, last.alpha_p, last.alpha_d,
+                      last.beta_c, last.p_obj, last.d_obj]})
+    if held[0] is not None:
+        restart(held[0])   # the restart due after the last timed body, now that its iterate is read
     timed_restarts = dict(restarts)
     if schur_live[1]:
         step = step_plain
         dev.set_timing(False)
-    # instrumented pass (per-stage HIP events, no graph replay) for the phase breakdown and the
-    # Schur-assembly roofline; not part of the timed region above
-    dev.set_timing(True)
-    n_inst = max(3, min(args.steps, 10))
-    schur_ms = 0.0
-    phase = np.zeros(_lib.NUM_STAGES)
-    inner = np.zeros(_lib.NUM_INNER)
-    for _ in range(n_inst):
-        st = step()
-        ph = np.array(st.phase_ms[:])
-        phase += ph
-        inner += np.array(st.inner_ms[:])
-        schur_ms += ph[_lib.STAGE_SCHUR]
-    barrier_sync()
-    dev.set_timing(False)
-    # host cost of enqueueing one loop body eagerly (launch by launch, no graph: the sharded
-    # path's default), i.e. the host time inside clrsdp_iterate_async; from the initial point,
-    # after the timed region
-    dev.restore_state()
-    barrier_sync()
-    dev.set_graph(False)
-    enq, body = [], []
-    for _ in range(12):
-        t1 = time.perf_counter()
-        dev.iterate_async(prm)
-        t2 = time.perf_counter()
-        dev.iterate_wait()
-        body.append(time.perf_counter() - t1)
-        enq.append(t2 - t1)
-    # back to the library's own default for this handle (the graph at fp64 unless
-    # CLRSDP_NO_GRAPH; eager at double-double / quad-double unless CLRSDP_GRAPH_MW)
-    dev.set_graph(not env_on("CLRSDP_NO_GRAPH") and (args.precision == 1 or env_on("CLRSDP_GRAPH_MW")))
-    host_enqueue_ms = float(np.median(enq[2:])) * 1e3
-    eager_body_ms = float(np.median(body[2:])) * 1e3
-    barrier_sync()
+    n_inst = 0
+    schur_ms = host_enqueue_ms = eager_body_ms = None
+    if args.full:
+        # instrumented pass (per-stage HIP events, no graph replay) for the phase breakdown and
+        # the Schur-assembly roofline; not part of the timed region above
+        dev.set_timing(True)
+        n_inst = max(3, min(args.steps, 10))
+        schur_ms = 0.0
+        phase = np.zeros(_lib.NUM_STAGES)
+        inner = np.zeros(_lib.NUM_INNER)
+        for _ in range(n_inst):
+            st = step()
+            ph = np.array(st.phase_ms[:])
+            phase += ph
+            inner += np.array(st.inner_ms[:])
+            schur_ms += ph[_lib.STAGE_SCHUR]
+        barrier_sync()
+        dev.set_timing(False)
+        # host cost of enqueueing one loop body eagerly (launch by launch, no graph: the sharded
+        # path's default), i.e. the host time inside clrsdp_iterate_async; from the initial
+        # point, after the timed region
+        dev.restore_state()
+        barrier_sync()
+        dev.set_graph(False)
+        enq, body = [], []
+        for _ in range(12):
+            t1 = time.perf_counter()
+            dev.iterate_async(prm)
+            t2 = time.perf_counter()
+            dev.iterate_wait()
+            body.append(time.perf_counter() - t1)
+            enq.append(t2 - t1)
+        # back to the library's own default for this handle (the graph at fp64 unless
+        # CLRSDP_NO_GRAPH; eager at double-double / quad-double unless CLRSDP_GRAPH_MW)
+        dev.set_graph(not env_on("CLRSDP_NO_GRAPH")
+                      and (args.precision == 1 or env_on("CLRSDP_GRAPH_MW")))
+        host_enqueue_ms = float(np.median(enq[2:])) * 1e3
+        eager_body_ms = float(np.median(body[2:])) * 1e3
+        barrier_sync()
     if dist is not None:
         dt = dist.max_over_ranks(dt)
-        schur_ms = dist.max_over_ranks(schur_ms)
-        host_enqueue_ms = dist.max_over_ranks(host_enqueue_ms)
-        eager_body_ms = dist.max_over_ranks(eager_body_ms)
+        if args.full:
+            schur_ms = dist.max_over_ranks(schur_ms)
+            host_enqueue_ms = dist.max_over_ranks(host_enqueue_ms)
+            eager_body_ms = dist.max_over_ranks(eager_body_ms)
     xranks, xbackend = dev.comm_info()
 
     if rank != 0:
@@ -360,17 +428,24 @@ def main():
     if world > 1:
         fl /= world   # per-rank share of the Schur work (the roofline is per GPU)
         by /= world
-    sch_s = schur_ms / 1e3 / n_inst
-    schur_src = "instrumented pass (per-stage events, no graph)"
+    if args.full:
+        sch_s = schur_ms / 1e3 / n_inst
+        schur_src = "instrumented pass (per-stage events, no graph)"
+    else:
+        sch_s = None
+        schur_src = "not timed: no device-clock stamps on this path (the instrumented pass of --full times it)"
     if schur_live[1] and schur_live[0] > 0.0:   # (the clock stamps exist on the fused fp64 path)
         sch_s = schur_live[0] / 1e3 / schur_live[1]
         schur_src = ("device clock (s_memrealtime): the sum over the SCHUR launches (at C3 the "
                      "one schur_fused_f64 launch; otherwise the V^T X^-1 and V^T Y GEMMs and the "
                      "pairs) of first workgroup start to last workgroup end, inside the replayed "
                      "graph, averaged over the timed region")
-    traffic, traffic_src = schur_pmc_traffic(args.config, args.precision, world, args.clusters)
-    issued, issued_src = schur_pmc_issued(args.config, args.precision, world, args.clusters)
-    achieved = fl / sch_s / 1e12   # in flops of the word type (multi-word flops when w > 1)
+    traffic = traffic_src = issued = issued_src = None
+    if args.full:
+        traffic, traffic_src = schur_pmc_traffic(args.config, args.precision, world, args.clusters)
+        issued, issued_src = schur_pmc_issued(args.config, args.precision, world, args.clusters)
+    # in flops of the word type (multi-word flops when w > 1)
+    achieved = fl / sch_s / 1e12 if sch_s else None
     peak = FP64_MFMA_PEAK_TFLOPS if args.precision == 1 else MW_VALU_PEAK_TFLOPS[args.precision]
     # the library takes the int8 (Ozaki) Schur products at double-double when every block has
     # m = 1 (clrsdp.hip build_ozaki) unless CLRSDP_OZAKI=0
@@ -418,28 +493,21 @@ def main():
                                      % OZAKI_DIGIT_PAIRS) if ozaki else
                                     "measured %s multiply-add ceiling x 2 (profiles/r01_mw_peak.log)"
                                     % DTYPES[args.precision],
-                     "frac": achieved / peak,
+                     "frac": achieved / peak if sch_s else None,
                      "issued_frac": issued, "issued_frac_source": issued_src,
                      "traffic": traffic,
                      "traffic_source": traffic_src,
                      "alg_bytes_per_iteration": by,
-                     "schur_ms_per_iteration": sch_s * 1e3,
+                     "schur_ms_per_iteration": sch_s * 1e3 if sch_s else None,
                      "schur_time_source": schur_src,
-                     "schur_alg_gbs": by / sch_s / 1e9},
-        "phase_ms_per_iteration": {n: float(v / n_inst) for n, v in zip(_lib.STAGE_NAMES, phase)},
-        # the reference's inner buckets (MPMP.jl:997-1012), same instrumented pass
-        "inner_ms_per_iteration": {n: float(v / n_inst) for n, v in zip(_lib.INNER_NAMES, inner)},
+                     "schur_alg_gbs": by / sch_s / 1e9 if sch_s else None},
+        "full": args.full,
         "graph_replay": graph_on,
         "exchange": "none (1 GPU)" if dist is None else dist.backend,
         # the communicator the library's loop body really uses: ranks from ncclCommCount on the
         # native RCCL path (clrsdp_comm_info), world_size on the callback path
         "exchange_ranks": xranks,
         "exchange_backend_native": xbackend,
-        "host_enqueue_ms": host_enqueue_ms,
-        "host_enqueue_source": ("median host time of clrsdp_iterate_async with the graph off "
-                                "(clrsdp_set_graph(0): the ~100 launches of one loop body enqueued "
-                                "eagerly, as the sharded path does), 10 bodies from the initial point"),
-        "eager_body_ms": eager_body_ms,
         # restarts from the post-warm-up snapshot inside the timed window, by cause: every
         # RESTART = 64 bodies, or once the last body's mu fell below MU_FLOOR = 1e-8 (the
         # stagnation regime); every timed step is still one full loop body
@@ -450,8 +518,19 @@ def main():
                       "synchronous (one hipGraph replay per loop body)" if graph_on else
                       "synchronous (loop body enqueued eagerly: the multi-word default)"),
     }
-    if world == 1 and not args.no_cpu:
-        res["cpu_baseline"] = cpu_baseline(pk, cons, b, bi, args.precision)
+    if args.full:
+        res.update({
+            "phase_ms_per_iteration": {n: float(v / n_inst) for n, v in zip(_lib.STAGE_NAMES, phase)},
+            # the reference's inner buckets (MPMP.jl:997-1012), same instrumented pass
+            "inner_ms_per_iteration": {n: float(v / n_inst) for n, v in zip(_lib.INNER_NAMES, inner)},
+            "host_enqueue_ms": host_enqueue_ms,
+            "host_enqueue_source": ("median host time of clrsdp_iterate_async with the graph off "
+                                    "(clrsdp_set_graph(0): the ~100 launches of one loop body enqueued "
+                                    "eagerly, as the sharded path does), 10 bodies from the initial point"),
+            "eager_body_ms": eager_body_ms,
+        })
+        if world == 1 and not args.no_cpu:
+            res["cpu_baseline"] = cpu_baseline(pk, cons, b, bi, args.precision)
     print(json.dumps(res), flush=True)
     dev.close()
     if dist is not None:

@@ -9,7 +9,8 @@
 #   tests[:PYTEST_K]        the -m gpu suite (optionally -k PYTEST_K), log tests.log
 #   testfile:FILE[:K]       one test file (optionally -k K), log tests_<file>.log
 #   micro:BIN[:ARGS]        a microbenchmark binary in microbin/ (hipcc line at the top of its tools/micro/*.hip)
-#   bench[:ARGS]            one bench.py line (ARGS with ',' for spaces), log bench_<n>.log
+#   bench[:ARGS]            one bench.py line (ARGS with ',' for spaces; --full among them for the
+#                           phase breakdown and the CPU baseline), log bench_<n>.log
 #   ab:ENV:R[:ARGS]         tools/ab.sh alternating A/B of ENV (ARGS with ',' for spaces)
 #   sweep:ARGS:ENV:ENV...   tools/env_sweep.sh: one bench run per setting (NONE = none)
 #   dist2                   2-rank bench rehearsal on one GPU (CLRSDP_BENCH_ONE_GPU=1)
@@ -56,7 +57,7 @@ for step in "$@"; do
     dist2)
       CLRSDP_BENCH_ONE_GPU=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 \
         --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 \
-        --steps 20 --warmup 3 > $OUT/dist2.log 2>&1; rc=$?
+        --steps 20 --warmup 3 --full > $OUT/dist2.log 2>&1; rc=$?
       echo "dist2 rc=$rc"; tail -1 $OUT/dist2.log | cut -c1-400 ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$n -o run -- \

@@ -18,10 +18,10 @@ cp gpurun_out/prof_$TAG/schur_pmc.json profiles/${TAG}_schur_pmc.json
 cp gpurun_out/prof_$TAG/schur_pmc.json $OUT/schur_pmc.json
 cp gpurun_out/prof_$TAG/kernels_pmc.json profiles/${TAG}_kernels_pmc.json
 cp gpurun_out/prof_$TAG/kernel_summary.txt profiles/${TAG}_c3_kernel_summary.txt
-timeout -k 10 200 python3 bench.py > $OUT/bench_c3_fp64.log 2>&1
-timeout -k 10 200 python3 bench.py --config c2 > $OUT/bench_c2_fp64.log 2>&1
-timeout -k 10 200 python3 bench.py --config c2 --precision 2 > $OUT/bench_c4_dd.log 2>&1
-timeout -k 10 200 python3 bench.py --config c5 --precision 4 > $OUT/bench_c5_qd.log 2>&1
+timeout -k 10 200 python3 bench.py --full > $OUT/bench_c3_fp64.log 2>&1
+timeout -k 10 200 python3 bench.py --full --config c2 > $OUT/bench_c2_fp64.log 2>&1
+timeout -k 10 200 python3 bench.py --full --config c2 --precision 2 > $OUT/bench_c4_dd.log 2>&1
+timeout -k 10 200 python3 bench.py --full --config c5 --precision 4 > $OUT/bench_c5_qd.log 2>&1
 # kernel summaries of the multi-word lines (C4 double-double, C5 quad-double)
 for cfg in "c4_dd:--config c2 --precision 2" "c5_qd:--config c5 --precision 4"; do
   name=${cfg%%:*}; args=${cfg#*:}
@@ -30,7 +30,7 @@ for cfg in "c4_dd:--config c2 --precision 2" "c5_qd:--config c5 --precision 4"; 
   python3 tools/prof_summary.py $OUT/kt_$name/run_kernel_stats.csv > $OUT/${name}_kernel_summary.txt
 done
 for c in 8 16 32; do
-  timeout -k 10 120 python3 bench.py --clusters $c --no-cpu --steps 300 > $OUT/clusters_$c.log 2>&1
+  timeout -k 10 120 python3 bench.py --full --clusters $c --no-cpu --steps 300 > $OUT/clusters_$c.log 2>&1
 done
 # kernel summary and per-body listing of the 8-cluster shard (the N = 8 rank's body)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_clusters8 -o run -- \
