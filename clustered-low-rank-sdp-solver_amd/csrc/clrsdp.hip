@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -1917,8 +1918,15 @@ struct Solver final : HandleBase {
   OzGemmDesc* d_ozg2 = nullptr;
   TileRef *d_ozs1t = nullptr, *d_ozs2t = nullptr, *d_ozg1t = nullptr, *d_ozg2t = nullptr;
   int n_ozs1 = 0, n_ozs2 = 0, n_ozg1 = 0, n_ozg2 = 0;
+  // the equilibration exponents of the contraction index (oz_split's kx): one arena, the del
+  // exponents of local block q at oz_kx + oz_kxoff[q] (-1: the block has no products)
+  int* oz_kx = nullptr;
+  std::vector<int64_t> oz_kxoff;
+  int64_t oz_nkx = 0;
   void build_ozaki() {
     use_oz = false;
+    oz_kx = nullptr;
+    oz_nkx = 0;
     if constexpr (std::is_same<T, mw::dd>::value) {
       if (anyMgt1 || lb.empty() || env_off("CLRSDP_OZAKI")) return;
       std::vector<OzSplitDesc> s1, s2;
@@ -1936,8 +1944,8 @@ struct Solver final : HandleBase {
         return E;
       };
       auto add_split = [&](std::vector<OzSplitDesc>& v, std::vector<TileRef>& t, const T* X, long long sv,
-                           long long sk, int nv, int K, signed char* D, int* E) {
-        v.push_back(OzSplitDesc{X, sv, sk, D, E, nv, K, pad(nv, 16), pad(K, 64)});
+                           long long sk, int nv, int K, signed char* D, int* E, const int* kx, int ks) {
+        v.push_back(OzSplitDesc{X, sv, sk, D, E, nv, K, pad(nv, 16), pad(K, 64), kx, ks, 0});
         for (int g = 0; g < cdiv(nv, 4); ++g) t.push_back(TileRef{(int)v.size() - 1, g});
       };
       auto add_gemm = [&](std::vector<OzGemmDesc>& v, std::vector<TileRef>& t, const signed char* DA,
@@ -1948,19 +1956,29 @@ struct Solver final : HandleBase {
         for (int q = 0; q < cdiv(M, 16) * tn; ++q)
           if (!upper || q / tn <= q % tn) t.push_back(TileRef{(int)v.size() - 1, q});
       };
-      for (const LBlk& b : lb) {
+      oz_kxoff.assign(lb.size(), -1);
+      oz_nkx = 0;
+      for (size_t q = 0; q < lb.size(); ++q)
+        if (lb[q].K > 0 && lb[q].del > 0) {
+          oz_kxoff[q] = oz_nkx;
+          oz_nkx += lb[q].del;
+        }
+      oz_kx = expo((int)oz_nkx);  // (zero until upload() sets them)
+      for (size_t q = 0; q < lb.size(); ++q) {
+        const LBlk& b = lb[q];
         const int n = b.n, del = b.del, K = b.K;
         if (K <= 0 || del <= 0) continue;
+        const int* kx = oz_kx + oz_kxoff[q];
         signed char *Dx = digits(n, del), *Dy = digits(n, del), *Gv = digits(K, del);
         signed char *Gtx = digits(K, del), *Gty = digits(K, del);
         int *Ex = expo(n), *Ey = expo(n), *Fv = expo(K), *Ftx = expo(K), *Fty = expo(K);
         // rows of X^-1_b, Y_b (n x n, ld n: row v, element k at v + k n); columns of V_b (del x K)
-        add_split(s1, s1t, Xinv + b.off, 1, n, n, del, Dx, Ex);
-        add_split(s1, s1t, Y + b.off, 1, n, n, del, Dy, Ey);
-        add_split(s1, s1t, V + b.voff, del, 1, K, del, Gv, Fv);
+        add_split(s1, s1t, Xinv + b.off, 1, n, n, del, Dx, Ex, kx, 1);
+        add_split(s1, s1t, Y + b.off, 1, n, n, del, Dy, Ey, kx, 1);
+        add_split(s1, s1t, V + b.voff, del, 1, K, del, Gv, Fv, kx, -1);
         // columns of TX_b, TY_b (del x K, ld n)
-        add_split(s2, s2t, TX + b.toff, n, 1, K, del, Gtx, Ftx);
-        add_split(s2, s2t, TY + b.toff, n, 1, K, del, Gty, Fty);
+        add_split(s2, s2t, TX + b.toff, n, 1, K, del, Gtx, Ftx, kx, 1);
+        add_split(s2, s2t, TY + b.toff, n, 1, K, del, Gty, Fty, kx, 1);
         const int Kp = pad(del, 64);
         add_gemm(g1, g1t, Dx, Ex, pad(n, 16), Gv, Fv, pad(K, 16), Kp, TX + b.toff, n, n, K, false);
         add_gemm(g1, g1t, Dy, Ey, pad(n, 16), Gv, Fv, pad(K, 16), Kp, TY + b.toff, n, n, K, false);
@@ -2090,12 +2108,14 @@ struct Solver final : HandleBase {
         fused_one = fused_one && fused_y;  // (instantiated with V^T Y on chip only)
         fused_d64 = fused_d64 && fused_one;   // (instantiated in the ONE form only)
         std::vector<TileRef> ft2d = tile_major(fnt);
-        if (fused_one) {  // every (row block a, tile s of its share): t = a + 64 s
+        if (fused_one) {  // every (row block a, tile s of its share): t = a + st s, st = max(64, nr)
+          // (the stride the kernel decodes with, schur_fused_f64: 64 up to 64 row blocks, K <= 4096,
+          // and the row-block count itself above, so that row blocks 64, 65, ... are launched too)
           std::vector<int> fnt1;
-          for (int nr : fnt) fnt1.push_back(64 * (nr / 2 + 1));
+          for (int nr : fnt) fnt1.push_back(std::max(64, nr) * (nr / 2 + 1));
           ft2d.clear();
           for (const TileRef& r : tile_major(fnt1)) {
-            const int nr = fnt[r.p], a = r.t % 64, sidx = r.t / 64;
+            const int nr = fnt[r.p], st = std::max(64, nr), a = r.t % st, sidx = r.t / st;
             const int nbt = (nr % 2 == 0 && a >= nr / 2) ? nr / 2 : nr / 2 + 1;
             if (a < nr && sidx < nbt) ft2d.push_back(r);
           }
@@ -2243,6 +2263,24 @@ struct Solver final : HandleBase {
           for (int p = 0; p < b.K; ++p) vt[p + (size_t)i * b.K] = src[i + (size_t)p * b.del];
         put(Vt + b.voff, vt.data(), (int64_t)vt.size(), 0, (int64_t)vt.size());
       }
+    }
+    // the Ozaki products' equilibration of the contraction index (oz_split): per row k of V_b the
+    // exponent of its largest entry, from the leading plane (0 for a row of zeros)
+    // (every block's into one host image of the arena, one copy)
+    if (oz_kx && oz_nkx > 0) {
+      std::vector<int> kx((size_t)oz_nkx, 0);
+      for (size_t q = 0; q < lb.size() && q < oz_kxoff.size(); ++q) {
+        const LBlk& b = lb[q];
+        if (oz_kxoff[q] < 0) continue;
+        const double* src = Vh + voff_g[b.gjl];
+        for (int i = 0; i < b.del; ++i) {
+          double mx = 0.0;
+          for (int p = 0; p < b.K; ++p) mx = std::max(mx, std::fabs(src[i + (size_t)p * b.del]));
+          if (mx > 0.0 && std::isfinite(mx)) kx[(size_t)oz_kxoff[q] + i] = std::ilogb(mx);
+        }
+      }
+      HIPCHK(hipMemcpyAsync(oz_kx, kx.data(), kx.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
     }
     for (int c = 0; c < nc(); ++c) {
       const int j = oc[c];

@@ -2422,7 +2422,7 @@ __device__ __forceinline__ int st_idx(int row, int col) { return row * 64 + (col
 // branch on d.grp: the branch made the rank-1 (C3) instance spill 92 B/lane at 256 VGPRs
 // (63.7 against 57.3 us per launch, round 6).
 // ONE (round 6, small batches): each workgroup forms TXt_a (and TYt_a) and then ONE column tile
-// s of row block a's share (tile ref t = a + 64 s) instead of all nb of them, so a batch with
+// s of row block a's share (tile ref t = a + max(64, T) s) instead of all nb of them, so a batch with
 // few row blocks (C2: 16 clusters x 4 = 64 workgroups, the 8-cluster shard: 32) spreads over
 // 2.5x the workgroups at the price of recomputing phase 1 per tile.
 // D64 (every block delta <= 64: C2): rows 64..127 of C' and k-chunks 16..31 of phase 2 are zero,
@@ -2444,12 +2444,13 @@ __global__ __launch_bounds__(512) void schur_fused_f64(const FusedPairDesc* __re
   auto P1 = [&](int img) { return sm_fused + (img ? VR : YR); };
   const TileRef tr = t2d[blockIdx.x];
   const FusedPairDesc d = descs[tr.p];
-  const int a = ONE ? tr.t % 64 : tr.t, K = d.K, D = d.del;
-  const int T = (K + 63) / 64, a0 = 64 * a;
+  const int K = d.K, D = d.del, T = (K + 63) / 64;
+  const int st1 = T > 64 ? T : 64;  // ONE: t = a + st1 s (the host's stride: K > 4096 has a >= 64)
+  const int a = ONE ? tr.t % st1 : tr.t, a0 = 64 * a;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nt = w & 3, h = w >> 2, lr = lane & 15, lk = lane >> 4;
   const int nb = (T % 2 == 0 && a >= T / 2) ? T / 2 : T / 2 + 1;  // tiles of this row block
-  const int s_lo = ONE ? tr.t / 64 : 0, s_hi = ONE ? s_lo + 1 : nb;  // the ones of this workgroup
+  const int s_lo = ONE ? tr.t / st1 : 0, s_hi = ONE ? s_lo + 1 : nb;  // the ones of this workgroup
   // ---------------- phase 1: C' = X^-1 V_a (and Y V_a)
   d4 c1[4], c1y[YV ? 4 : 1];
 #pragma unroll

@@ -828,7 +828,18 @@ __global__ __launch_bounds__(256) void potrf_blk_update(const BlkPotrfDesc<T>* _
 // every level-L sum of int8 products accumulates exactly in int32 (|.| <= 16 Kpad 64^2 < 2^31 for
 // Kpad < 2^15) on v_mfma_i32_16x16x64_i8 and converts exactly to fp64; the OZ_S levels are summed
 // in double-double, smallest first.  Levels L >= OZ_S are dropped: ~2^-7 OZ_S = 2^-112 relative
-// to 2^(E_i + F_j) K -- a row / column-normwise bound, where the VALU GEMM's is componentwise.
+// to 2^(E_i + F_j) K -- a bound in the largest |a_ik| of row i times the largest |b_kj| of column
+// j, where the VALU GEMM's is componentwise (sum_k |a_ik| |b_kj|).  The two differ by the spread of
+// the operands along k: with V = D R, X^-1 = D^-1 M D^-1 and D = diag(2^(-g k)) -- the grading a
+// monomial-type basis gives an interior-point iterate -- the largest a_ik and the largest b_kj sit
+// at opposite ends of k and every product a_ik b_kj is smaller than the bound's scale by the span
+// of D (2^44 at delta = 12, g = 4: 2^-68 instead of 2^-112 relative to the entry).  So the
+// contraction index is equilibrated, exactly, before the split: element k of every vector is
+// multiplied by 2^(ks kx[k]), kx[k] = the exponent of the largest |V_kj| of row k of V_b (set once
+// from the uploaded V), ks = -1 for the columns of V_b and +1 for the rows of X^-1_b, Y_b and the
+// columns of TX_b, TY_b; the products a_ik b_kj are unchanged and E, F are those of the scaled
+// vectors.  After it the bound's scale is within a small factor of sum_k |a_ik| |b_kj| whenever
+// the grading of the operands is the basis's (what is left is the spread of R and M themselves).
 // 136 int8 MFMAs per 16 x 16 tile and 64-k chunk against 64 double-double FMAs per output and k
 // on the VALU: 9.1 against 15.0 us for 16 products 64 x 64 @ 64 x 128, 15.1 against 43.0 us for
 // 64 (tools/micro/ozaki_dd_bench.hip, same accuracy against a host double-double reference).
@@ -845,6 +856,8 @@ struct OzSplitDesc {
   signed char* D;      // digit planes, [OZ_S][Rpad][Kpad]
   int* E;              // per-vector exponent
   int nv, K, Rpad, Kpad;
+  const int* kx;       // per-k equilibration exponents (K of them), element k scaled by 2^(ks kx[k])
+  int ks, pad;
 };
 // one wave per vector (4 per workgroup); t2d: TileRef{desc, group of 4 vectors}
 __global__ __launch_bounds__(256) void oz_split(const OzSplitDesc* __restrict__ descs,
@@ -857,14 +870,15 @@ __global__ __launch_bounds__(256) void oz_split(const OzSplitDesc* __restrict__ 
   int ex = -1100;
   for (int k = lane; k < d.K; k += 64) {
     const double h = x[(size_t)k * d.sk].hi;
-    if (h != 0.0) ex = max(ex, ilogb(h));
+    if (h != 0.0) ex = max(ex, ilogb(h) + d.ks * d.kx[k]);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) ex = max(ex, __shfl_xor(ex, o));
-  const int E = ex + 2;  // |x| < 2^(ex+1) = 2^E / 2
+  const int E = ex + 2;  // |x 2^(ks kx)| < 2^(ex+1) = 2^E / 2
   for (int k = lane; k < d.K; k += 64) {
     const mw::dd a = x[(size_t)k * d.sk];
-    double h = ldexp(a.hi, -E), l = ldexp(a.lo, -E);
+    const int sh = d.ks * d.kx[k] - E;
+    double h = ldexp(a.hi, sh), l = ldexp(a.lo, sh);
     signed char* out = d.D + (size_t)v * d.Kpad + k;
 #pragma unroll
     for (int p = 0; p < OZ_S; ++p) {

@@ -142,6 +142,159 @@ def residual_scales(cons, b, X):
             "d": float(max(np.max(np.abs(np.array(c.c, dtype=float))) for c in cons))}
 
 
+def _sample_sums(M, starts, counts):
+    """Sums of the rows and columns of the K x K matrix M over the rank groups of the samples
+    (N x N): group k holds rows starts[k] .. starts[k] + counts[k] - 1 (none when the rank is 0)."""
+    nz = counts > 0
+    out = np.zeros((len(counts), len(counts)), dtype=M.dtype)
+    if nz.any():
+        R = np.add.reduceat(M, starts[nz], axis=0)
+        out[np.ix_(nz, nz)] = np.add.reduceat(R, starts[nz], axis=1)
+    return out
+
+
+def _ld_gemm_nt(A, Bt, threads=8):
+    """A @ Bt.T for C-contiguous longdouble A (M x k) and Bt (N x k).  numpy has no BLAS for
+    longdouble; its einsum loop over two contiguous rows is the fastest form it has, and it
+    releases the GIL, so row slabs of A go to a few threads (K = 4098, k = 65: 0.4 s against the
+    4.5 s of V.T @ TX).  The sums of each entry are the same whatever the slabs."""
+    from concurrent.futures import ThreadPoolExecutor
+    A, Bt = np.ascontiguousarray(A), np.ascontiguousarray(Bt)
+    out = np.empty((A.shape[0], Bt.shape[0]), dtype=A.dtype)
+    if A.shape[0] * Bt.shape[0] < 1 << 16:
+        out[...] = np.einsum("ik,jk->ij", A, Bt)
+        return out
+    edges = np.linspace(0, A.shape[0], 4 * threads + 1).astype(int)
+
+    def slab(q):
+        out[edges[q]:edges[q + 1]] = np.einsum("ik,jk->ij", A[edges[q]:edges[q + 1]], Bt)
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(slab, range(4 * threads)))
+    return out
+
+
+def schur_dense(cons, bi, X_inv, Y):
+    """Dense restatement of the SCHUR stage (the 4-term formula, MPMP.jl:1373-1398, as
+    oracle/mpmp_oracle.py:compute_S_integrated assembles it): V, X^-1 and Y taken as float64, every
+    product and sum accumulated in np.longdouble, all of it as GEMMs, Hadamard products and group
+    sums -- usable at K of several thousand, where the oracle's per-entry code is not.
+    Returns (S, A_Y) as flat longdouble arrays in the layout of BUF_S and BUF_AY."""
+    ld = np.longdouble
+    S_out, AY_out = [], []
+    for j in range(bi.J):
+        m, N, D = bi.m[j], bi.n_samples[j], bi.dim_S[j]
+        Sj = np.zeros((D, D), dtype=ld)
+        for l in range(bi.L[j]):
+            cl = cons[j]
+            V = np.stack([np.asarray(v, dtype=np.float64) for vk in cl.A[l] for v in vk], axis=1).astype(ld)
+            lam = np.array([float(x) for hk in cl.H[l] for x in hk], dtype=np.float64).astype(ld)
+            counts = np.array([len(vk) for vk in cl.A[l]], dtype=np.int64)
+            starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+            delta, K = V.shape
+            Xi = np.asarray(X_inv[j][l], dtype=np.float64).astype(ld)
+            Yb = np.asarray(Y[j][l], dtype=np.float64).astype(ld)
+            blk = lambda M, r, s: M[r * delta:(r + 1) * delta, s * delta:(s + 1) * delta]
+            Vt = np.ascontiguousarray(V.T)
+            BX = [[_ld_gemm_nt(Vt, (blk(Xi, r, s) @ V).T) for s in range(m)] for r in range(m)]
+            BY = [[_ld_gemm_nt(Vt, (blk(Yb, r, s) @ V).T) for s in range(m)] for r in range(m)]
+            AY_out += [np.diagonal(BY[r][s]).copy() for r in range(m) for s in range(r + 1)]
+            LL = np.outer(lam, lam) / 4
+            for r1 in range(m):
+                for s1 in range(r1 + 1):
+                    for r2 in range(m):
+                        for s2 in range(r2 + 1):
+                            T = (BX[s1][r2] * BY[s2][r1].T + BX[r1][r2] * BY[s2][s1].T
+                                 + BX[s1][s2] * BY[r2][r1].T + BX[r1][s2] * BY[r2][s1].T)
+                            h0 = (s1 + r1 * (r1 + 1) // 2) * N
+                            v0 = (s2 + r2 * (r2 + 1) // 2) * N
+                            Sj[v0:v0 + N, h0:h0 + N] += _sample_sums(LL * T, starts, counts).T
+        Sup = np.triu(Sj)   # Symmetric(S_j) from its upper triangle (MPMP.jl:1409)
+        S_out.append((Sup + np.triu(Sj, 1).T).reshape(-1, order="F"))
+    return np.concatenate(S_out), np.concatenate(AY_out)
+
+
+# ---- graded data: componentwise parity of the Schur products --------------------------------
+def graded_instance(pk, delta, rank, N, g, seed):
+    """One m = 1 cluster on the grading a monomial-type basis gives an interior-point iterate:
+    synth's V, lambda and B with component i of every v multiplied by 2^(-g i) (exact), and a
+    state X = D Mx D, Y = D^-1 My D^-1 with D = diag(2^(-g i)) and Mx, My seeded SPD (rand_spd,
+    symmetric float64; the scalings are exact too).  Not feasible -- for the MU_R, XINV and SCHUR
+    stages only.  Returns (constraints, b, (x, X, y, Y))."""
+    cons, b = pk.synth(seed=seed, J=1, L=1, delta=delta, rank=rank, n_y=2, N=N)
+    d = np.ldexp(1.0, -g * np.arange(delta))
+    cl = cons[0]
+    cl.A = [[[np.asarray(v, dtype=float) * d for v in vk] for vk in cl.A[0]]]
+    rng = np.random.default_rng(seed)
+    sym = lambda M: (M + M.T) / 2
+    Mx, My = sym(rand_spd(delta, rng)), sym(rand_spd(delta, rng))
+    X = d[:, None] * Mx * d[None, :]
+    Y = My / d[:, None] / d[None, :]
+    return cons, b, (np.zeros(N), [[X]], np.zeros(2), [[Y]])
+
+
+def _exact_ints(a):
+    """(object array of Python ints I, exponent e) with a = I 2^e exactly, for an array of
+    float64 or mpmath.mpf values."""
+    import mpmath
+    a = np.asarray(a)
+    parts = []
+    for v in a.ravel():
+        sign, man, exp, _ = (v if isinstance(v, mpmath.mpf) else mpmath.mpf(float(v)))._mpf_
+        parts.append((-int(man) if sign else int(man), int(exp)))
+    e = min([ex for mn, ex in parts if mn] + [0])
+    out = np.empty(a.size, dtype=object)
+    for i, (mn, ex) in enumerate(parts):
+        out[i] = mn << (ex - e) if mn else 0
+    return out.reshape(a.shape), e
+
+
+def schur_exact(cl, X_inv, Y, prec=256):
+    """S and A_Y of one m = 1, L = 1 cluster from the given X^-1 (float64 or mpf entries, e.g. a
+    device's own), Y, V and lambda (float64): the 4-term formula (MPMP.jl:1373-1398) at m = 1,
+    S[k2, k1] = sum lambda_1 lambda_2 BX[rho_1, rho_2] BY[rho_2, rho_1] over rho_i in sample k_i,
+    upper triangle mirrored, A_Y = diag(BY), with BX = V^T X^-1 V and BY = V^T Y V.  Every
+    operand is a dyadic rational, so all of it is done in exact integer arithmetic and rounded
+    once to ``prec`` bits of mpmath.mpf.  Also returns the componentwise bounds of both (float64):
+    the same formulas with every factor replaced by its absolute value."""
+    import mpmath
+    V = np.stack([np.asarray(v, dtype=float) for vk in cl.A[0] for v in vk], axis=1)
+    lam = np.array([float(x) for hk in cl.H[0] for x in hk])
+    counts = np.array([len(vk) for vk in cl.A[0]], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    Vi, ev = _exact_ints(V)
+    Xi, ex = _exact_ints(X_inv)
+    Yi, ey = _exact_ints(Y)
+    li, el = _exact_ints(lam)
+    BX = Vi.T @ (Xi @ Vi)
+    BY = Vi.T @ (Yi @ Vi)
+    Sg = _sample_sums(np.outer(li, li) * (BX * BY.T), starts, counts).T
+    N = len(counts)
+    iu = np.triu_indices(N, 1)
+    Sg[(iu[1], iu[0])] = Sg[iu]
+    eS, eA = 2 * el + 4 * ev + ex + ey, 2 * ev + ey
+    with mpmath.workprec(prec):
+        S = np.array([mpmath.ldexp(mpmath.mpf(int(v)), eS) for v in Sg.reshape(-1, order="F")], dtype=object)
+        AY = np.array([mpmath.ldexp(mpmath.mpf(int(v)), eA) for v in np.diagonal(BY)], dtype=object)
+    aV = np.abs(V)
+    absf = lambda M: np.abs(np.array([[float(v) for v in r] for r in np.asarray(M)]))
+    bX, bY = aV.T @ absf(X_inv) @ aV, aV.T @ absf(Y) @ aV
+    bS = _sample_sums(np.outer(np.abs(lam), np.abs(lam)) * (bX * bY.T), starts, counts).T
+    bS[(iu[1], iu[0])] = bS[iu]
+    return S, AY, bS.reshape(-1, order="F"), np.diagonal(bY).copy()
+
+
+def cw_err(got, ref, bound):
+    """Componentwise error: the maximum over entries of |got - ref| / bound, in mpmath at 320
+    bits (whatever the global precision is)."""
+    import mpmath
+    g, r = np.asarray(got, dtype=object).ravel(), np.asarray(ref, dtype=object).ravel()
+    bd = np.asarray(bound, dtype=float).ravel()
+    assert len(g) == len(r) == len(bd)
+    with mpmath.workprec(320):
+        return float(max([abs(mpmath.mpf(x) - mpmath.mpf(y)) / mpmath.mpf(float(s))
+                          for x, y, s in zip(g, r, bd)] + [mpmath.mpf(0)]))
+
+
 # ---- sampled fixtures of large stage outputs (tests/golden/make_stage_fixtures.py) ----------
 SKETCH_MULT = (0x9E3779B1, 0x85EBCA77)
 

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from helpers import (CONFIGS_SMALL, compare_summary, poly_min_instance, rand_spd, rel_err, residual_scales,
-                     stage_device, stage_reference)
+                     schur_dense, stage_device, stage_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +77,11 @@ def _stage_compare_fixture(pk, name, words, tol, bits=256):
     sc = residual_scales(cons, b, state[1])
     e = {k: compare_summary(got[k], rec, sc.get(k, 0.0)) for k, rec in fx["buffers"].items()}
     print(name, words, bits, " ".join(f"{k}={v:.1e}" for k, v in e.items()))
+    if isinstance(tol, dict):  # per-buffer tolerances: the measured ratios before the assertion
+        print(name, "error / tolerance:", " ".join(f"{k}={v / tol[k]:.2g}" for k, v in e.items()))
+        bad = {k: (v, tol[k]) for k, v in e.items() if not v <= tol[k]}
+        assert not bad, f"stage parity failures vs mp{bits} (error, tolerance): {bad}"
+        return e
     bad = {k: v for k, v in e.items() if not v <= tol}
     assert not bad, f"stage parity failures vs mp{bits}: {bad}"
     return e
@@ -203,6 +208,127 @@ def test_schur_fused_matches_unfused(pk, monkeypatch):
             off += D * D
 
 
+_WIDE_REF = {}
+
+
+def _wide_schur_case(pk, delta, rank, N):
+    """One cluster of N samples (K = rank N columns in V), its initial point, and the dense
+    longdouble reference of S and A_Y at that point (helpers.schur_dense), computed once per
+    shape and left unchanged."""
+    key = (delta, rank, N)
+    if key not in _WIDE_REF:
+        cons, b = pk.synth(seed=11, J=1, L=1, delta=delta, rank=rank, n_y=2, N=N)
+        bi = pk.get_block_info(cons)
+        st = pk.initial_point(bi, 10.0, 10.0)
+        Xi = [[np.linalg.inv(np.asarray(Xb, dtype=float)) for Xb in Xj] for Xj in st[1]]
+        _WIDE_REF[key] = (cons, b, bi, st) + schur_dense(cons, bi, Xi, st[3])
+    return _WIDE_REF[key]
+
+
+@pytest.mark.parametrize("delta,rank,N,env", [
+    (65, 2, 2048, {}),                               # K = 4096: 64 row blocks, the ONE form
+    (65, 2, 2049, {}),                               # K = 4098: 65 row blocks, ONE, group-sum epilogue
+    (40, 2, 2049, {}),                               # K = 4098: ONE, the D64 instance
+    (72, 1, 4097, {}),                               # K = 4097: 65 row blocks, the last one ragged; direct S
+    # the multi-tile form at the same K (65 row blocks are below the 128 at which the library
+    # takes it by itself, so the fused kernel is forced as well: without that, ONE=0 alone
+    # gives the unfused pair of the next row)
+    (65, 2, 2049, {"CLRSDP_SCHUR_FUSED": "1", "CLRSDP_SCHUR_FUSED_ONE": "0"}),
+    (65, 2, 2049, {"CLRSDP_SCHUR_FUSED": "0"}),      # the unfused pair at the same K
+], ids=["K4096-one", "K4098-one-grp2", "K4098-one-d64", "K4097-one-direct", "K4098-multi", "K4098-unfused"])
+def test_schur_stage_beyond_64_row_blocks(pk, monkeypatch, delta, rank, N, env):
+    """The SCHUR stage of one cluster with K > 4096 columns in V, i.e. more than 64 row blocks of
+    64: with fewer than 128 row blocks in the batch the library takes the one-tile fused form by
+    itself, whose tile reference a + 64 s dropped row blocks 64 and above (their part of S_j and
+    A_Y was never written, and no error raised).  S and A_Y against the dense longdouble
+    restatement of the 4-term formula at the fp64 tolerance; the S_j the kernel writes directly
+    (rank 1) is exactly symmetric.  K = 4096 is the last size the old encoding covered; the
+    multi-tile form and the unfused pair are pinned at the same K."""
+    from clrsdp_amd import _lib as L
+    for k in ("CLRSDP_SCHUR_FUSED", "CLRSDP_SCHUR_FUSED_ONE", "CLRSDP_SCHUR_FUSED_D64", "CLRSDP_SCHUR_GRP2"):
+        monkeypatch.delenv(k, raising=False)  # (the library's own choice of path unless env says so)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cons, b, bi, st, S_ref, AY_ref = _wide_schur_case(pk, delta, rank, N)
+    P = pk.make_params("0.3", "0.1", "0.7", 0)
+    dev = pk.DeviceSolver(cons, b, bi)
+    try:
+        dev.set_state(*st)
+        for stage in (L.STAGE_MU_R, L.STAGE_XINV, L.STAGE_SCHUR):
+            dev.run_stage(stage, P, False)
+        S = np.asarray(dev.buffer(L.BUF_S, False), dtype=float)
+        AY = np.asarray(dev.buffer(L.BUF_AY, False), dtype=float)
+    finally:
+        dev.close()
+    eS, eA = rel_err(S, S_ref), rel_err(AY, AY_ref)
+    print(f"K={rank * N} delta={delta} {env}: rel_err S {eS:.2e}  A_Y {eA:.2e}")
+    assert eS <= TOL64 and eA <= TOL64, (eS, eA)
+    if rank == 1:
+        blk = S.reshape(N, N)
+        assert np.array_equal(blk, blk.T)
+
+
+GRADED_CASES = [(12, 1, 23, 0), (12, 1, 23, 4), (40, 2, 79, 0), (40, 2, 79, 1)]  # spans 2^0, 2^44, 2^0, 2^39
+
+
+@pytest.mark.parametrize("delta,rank,N,g", GRADED_CASES,
+                         ids=[f"delta{d}-rank{r}-g{g}" for d, r, _, g in GRADED_CASES])
+@pytest.mark.parametrize("words,env", [
+    (2, {}),                                                       # the int8 (Ozaki) products, the default
+    (2, {"CLRSDP_OZAKI": "0"}),                                    # the VALU products
+    (1, {}),                                                       # fp64: the one-tile fused form (D64 instance)
+    (1, {"CLRSDP_SCHUR_FUSED": "1", "CLRSDP_SCHUR_FUSED_ONE": "0"}),  # fp64: the multi-tile fused form
+    (1, {"CLRSDP_SCHUR_FUSED": "0"}),                              # fp64: the unfused pair
+], ids=["dd", "dd-valu", "fp64", "fp64-multi", "fp64-unfused"])
+def test_schur_products_componentwise_on_graded_data(pk, monkeypatch, words, delta, rank, N, g, env):
+    """The Schur products on the grading a monomial-type basis gives an interior-point iterate
+    (helpers.graded_instance: V = D R, X = D Mx D, Y = D^-1 My D^-1, D = diag(2^(-g i))),
+    measured componentwise: max |S - S_ref| / s over the entries, with S_ref from the device's own
+    X^-1 and the exact Y, V, lambda (helpers.schur_exact, so the conditioning of the inversion
+    stays out) and s the same formula on absolute values, (|V|^T |X^-1| |V|) o (|V|^T |Y| |V|)
+    summed over the rank pairs with |lambda| weights.  The metric max|err| / max|ref| of the other
+    tests divides by the largest entry and by construction cannot see a normwise product.
+
+    Bound 8 (delta + 2) u, u = 2^-104 for double-double (csrc/mwfloat.h), 2^-53 for fp64: each
+    factor is two chained length-delta dot products (gamma_delta ~ delta u each), two factors,
+    the Hadamard product and the group sum add 2 u: 4 (delta + 2) u less second-order terms,
+    and a factor 2 of slack.  The int8 (Ozaki) products, the double-double default at m = 1, are
+    normwise per row and column of each product; they hold this bound on graded data only with
+    the contraction index equilibrated before the split (oz_split's kx).  The g = 0 rows and
+    CLRSDP_OZAKI=0 (the VALU products, componentwise by construction) are the controls that show
+    the bound is attainable; at words = 1 the same cases pin the three fp64 Schur paths: the
+    one-tile fused form these small batches take by default, the multi-tile fused form and the
+    unfused pair (the environments of test_schur_stage_beyond_64_row_blocks).  The default rows
+    run with the path switches unset, so the library's own choice is what is measured."""
+    from clrsdp_amd import _lib as L
+    from helpers import cw_err, graded_instance, schur_exact
+    for k in ("CLRSDP_OZAKI", "CLRSDP_SCHUR_FUSED", "CLRSDP_SCHUR_FUSED_ONE"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cons, b, st = graded_instance(pk, delta, rank, N, g, seed=21)
+    bi = pk.get_block_info(cons)
+    P = pk.make_params("0.3", "0.1", "0.7", 0)
+    exact = words > 1
+    dev = pk.DeviceSolver(cons, b, bi, precision_words=words)
+    try:
+        dev.set_state(*st)
+        for stage in (L.STAGE_MU_R, L.STAGE_XINV, L.STAGE_SCHUR):
+            dev.run_stage(stage, P, False)
+        Xi = np.array(dev.buffer(L.BUF_XINV, exact), dtype=object if exact else float)
+        S = np.array(dev.buffer(L.BUF_S, exact), dtype=object if exact else float)
+        AY = np.array(dev.buffer(L.BUF_AY, exact), dtype=object if exact else float)
+    finally:
+        dev.close()
+    S_ref, AY_ref, bS, bA = schur_exact(cons[0], Xi.reshape(delta, delta, order="F"), st[3][0][0])
+    u = 2.0 ** -104 if words == 2 else 2.0 ** -53
+    tol = 8 * (delta + 2) * u
+    eS, eA = cw_err(S, S_ref, bS), cw_err(AY, AY_ref, bA)
+    print(f"words={words} delta={delta} rank={rank} g={g} {env}: componentwise error / bound: "
+          f"S {eS / tol:.3g}  A_Y {eA / tol:.3g}  (S: 2^{np.log2(max(eS, 1e-300)):.1f})")
+    assert eS <= tol and eA <= tol, (eS / tol, eA / tol)
+
+
 def test_stage_parity_sphere_packing_shape(pk, oracle):
     """Mixed block sizes 1..18, m = 2 and m = 1 clusters, 2 blocks per cluster (config 5 shape)."""
     cons, b = pk.synth_mixed(**pk.SPHERE_PACKING_SHAPE, seed=1)
@@ -266,6 +392,31 @@ def test_stage_parity_dd_c4_shape(pk, bits, variant, monkeypatch):
     monkeypatch.setenv("CLRSDP_POTRF_BLK", "0" if variant == "one-cu-potrf" else "1")
     monkeypatch.setenv("CLRSDP_OZAKI", "0" if variant == "valu-products" else "1")
     _stage_compare_fixture(pk, "c4dd", 2, 1e-25, bits)
+
+
+@pytest.mark.parametrize("variant", ["default", "valu-products", "one-cu-potrf", "full-pairs"])
+def test_stage_parity_dd_late_iterate(pk, variant, monkeypatch):
+    """Double-double on an ill-conditioned late iterate (fixture c4late: J = 2, delta = 40, rank 2,
+    n_y = 24, dim_S = 79 -- five 16-column panels of the blocked potrf, the last 15 wide -- after
+    23 bodies of the CPU restatement at words = 2; kappa_1(S_j) ~ 1e15..1e18, recorded in the
+    fixture), where potrf_blk_trsm's product with the explicit L_kk^-1 has a backward error that
+    grows with kappa(L_kk).  Every stage buffer against the 256-bit oracle, at
+    max(1e-25, 16 ref_err_mp106): ref_err_mp106 is the same oracle body run at 106 bits (the
+    reference algorithm at the device's own precision) against the 256-bit record; x4 for
+    double-double's 2^-104 roundoff against 2^-106 and x4 for Cholesky + L^-1 against the
+    oracle's pivoted LU elimination order.  The variants of test_stage_parity_dd_c4_shape."""
+    import gzip
+    # (the default variant with every switch unset: the library's own defaults, not forced values)
+    for k, off in (("CLRSDP_MW_PAIR_UPPER", "full-pairs"), ("CLRSDP_POTRF_BLK", "one-cu-potrf"),
+                   ("CLRSDP_OZAKI", "valu-products")):
+        monkeypatch.delenv(k, raising=False)
+        if variant == off:
+            monkeypatch.setenv(k, "0")
+    with gzip.open(os.path.join(GOLDEN, "stage_c4late_mp256.json.gz"), "rt") as f:
+        fx = json.load(f)
+    tol = {k: max(1e-25, 16 * fx["ref_err_mp106"][k]) for k in fx["buffers"]}
+    print("c4late", variant)
+    _stage_compare_fixture(pk, "c4late", 2, tol, 256)
 
 
 def test_stage_parity_qd_twin(pk):

@@ -40,6 +40,52 @@ def test_schur_equals_dense_trace_formula(pk, oracle, cfg):
         assert np.allclose(S[j], S[j].T, rtol=0, atol=1e-14 * np.abs(S[j]).max())
 
 
+@pytest.mark.parametrize("cfg", [CONFIGS_SMALL[0], CONFIGS_SMALL[2], CONFIGS_SMALL[1]],
+                         ids=["rank1", "rank2", "m2L2"])
+def test_dense_schur_helper_matches_oracle(pk, oracle, cfg):
+    """helpers.schur_dense (longdouble GEMMs: the reference of the K > 4096 Schur-stage GPU tests)
+    against the oracle's own compute_T_decomposition(...).S_raw and A_Y on a random SPD state, in
+    the flat buffer layout of helpers.stage_reference."""
+    from helpers import schur_dense
+    cons, b = pk.synth(seed=5, **cfg)
+    bi = oracle.get_block_info(cons)
+    X, Y = _random_state(bi, np.random.default_rng(2))
+    ar = oracle.Fp64()
+    Xi = oracle.xinv(ar, X)
+    dec, AY = oracle.compute_T_decomposition(ar, cons, Xi, Y, bi)
+    S_ref = np.concatenate([s.reshape(-1, order="F") for s in dec.S_raw])
+    AY_ref = np.concatenate([AY[j][l][r][s] for j in range(bi.J) for l in range(bi.L[j])
+                             for r in range(bi.m[j]) for s in range(r + 1)])
+    S, A_Y = schur_dense(cons, bi, Xi, Y)
+    assert S.dtype == np.longdouble and S.shape == S_ref.shape and A_Y.shape == AY_ref.shape
+    assert rel_err(S, S_ref) < 1e-13
+    assert rel_err(A_Y, AY_ref) < 1e-13
+
+
+def test_exact_schur_reference_matches_mp_oracle(pk, oracle):
+    """helpers.schur_exact (exact integers, one rounding to 256 bits: the reference of the
+    graded-data GPU tests) against oracle.Mp(256)'s S and A_Y at g = 0 from the same 256-bit
+    X^-1.  The oracle rounds every operation at 256 bits, so the two agree to a few hundred
+    units of 2^-256 of the componentwise bound, not bitwise: 2^-240 asserted."""
+    from helpers import cw_err, graded_instance, schur_exact
+    cons, b, st = graded_instance(pk, 12, 1, 23, 0, seed=21)
+    ar = oracle.Mp(256)
+    bi = oracle.get_block_info(cons)
+    consm = [pk.Cluster([[[ar.asarray(v) for v in vk] for vk in Al] for Al in cl.A], ar.asarray(cl.B),
+                        ar.asarray(cl.c), [[[ar.num(x) for x in hk] for hk in Hl] for Hl in cl.H])
+             for cl in cons]
+    Xi = oracle.xinv(ar, [[ar.asarray(st[1][0][0])]])
+    Ym = [[ar.asarray(st[3][0][0])]]
+    S_o, AY_o = oracle.compute_S_integrated(ar, consm, Xi, Ym, bi)
+    S, AY, bS, bA = schur_exact(cons[0], Xi[0][0], st[3][0][0])
+    assert cw_err(S_o[0].reshape(-1, order="F"), S, bS) <= 2.0 ** -240
+    assert cw_err(AY_o[0][0][0][0], AY, bA) <= 2.0 ** -240
+    # and the float64 restatement at longdouble agrees with it too (two independent routes)
+    from helpers import schur_dense
+    S_d, AY_d = schur_dense(cons, bi, [[np.array(Xi[0][0], dtype=float)]], st[3])
+    assert cw_err(S_d.astype(float), S, bS) <= 1e-14 and cw_err(AY_d.astype(float), AY, bA) <= 1e-14
+
+
 @pytest.mark.parametrize("cfg", CONFIGS_SMALL)
 def test_trace_and_weighted_A_are_adjoint(pk, oracle, cfg):
     """<sum_i a_i A_i, Z> = a . Tr(A_* Z)  (MPMP.jl:1517-1584 vs 1621-1678), and both match the
@@ -223,6 +269,40 @@ def test_stage_fixtures_agree_with_fp64_oracle(pk, oracle, name, bits):
     sc = residual_scales(cons, b, state[1])
     e = {k: compare_summary(ref[k], rec, sc.get(k, 0.0)) for k, rec in fx["buffers"].items()}
     assert max(e.values()) < 1e-9, e
+
+
+def test_late_stage_fixture_agrees_with_fp64_oracle(pk, oracle):
+    """The late double-double fixture (c4late, make_stage_fixtures.make_late) is consistent with
+    the fp64 oracle started from its state rounded to float64, on the early buffers mu and R --
+    a stale or mis-indexed fixture is caught without a GPU.  mu = <X, Y> / n to 1e-9; R = mu_p I
+    - X Y cancels to the size of mu, so to 1e-9 kappa with kappa = the largest kappa_1 of the X
+    and Y blocks recorded in the fixture (never looser than 1e-3).  The recorded iterate is
+    qualified: max kappa_1(S_j) in [1e15, 1e18]."""
+    import gzip
+    import importlib.util
+
+    from helpers import compare_summary
+    spec = importlib.util.spec_from_file_location("make_stage_fixtures",
+                                                  os.path.join(GOLDEN, "make_stage_fixtures.py"))
+    M = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(M)
+    sf = os.path.join(GOLDEN, "stage_c4late.npz")
+    with gzip.open(os.path.join(GOLDEN, "stage_c4late_mp256.json.gz"), "rt") as f:
+        fx = json.load(f)
+    assert 20 <= fx["late_iters"] <= 30 and 1e15 <= max(fx["kappa1"]["S"]) <= 1e18
+    assert set(fx["ref_err_mp106"]) == set(fx["buffers"])
+    cons, b = M.instance("c4late", sf)
+    bi = oracle.get_block_info(cons)
+    x, X, y, Y = M.load_state(sf, bi)
+    f64 = lambda a: np.array(a, dtype=float)
+    X64, Y64 = [[f64(B) for B in Bj] for Bj in X], [[f64(B) for B in Bj] for Bj in Y]
+    ar = oracle.Fp64()
+    mu = oracle.dot_blocks(ar, X64, Y64) / bi.total_dim
+    R = oracle.compute_residual_R(ar, X64, Y64, oracle._param(ar, oracle.DEFAULTS["beta_infeasible"]) * mu)
+    from clrsdp_amd import instance as inst
+    kappa = max(fx["kappa1"]["X"] + fx["kappa1"]["Y"])
+    assert compare_summary(np.array([mu]), fx["buffers"]["mu"]) < 1e-9
+    assert compare_summary(inst.blocks_to_flat(R), fx["buffers"]["R"]) < min(1e-9 * kappa, 1e-3)
 
 
 @pytest.mark.parametrize("name", ["kw_C_b0_mp256", "kw_needp_mp256", "kw_needd_mp256",
