@@ -565,6 +565,11 @@ struct TrsmPlan : PlanBase {
   // (W = L^-1 B) take 16 (one diagonal pass of 256 threads, and four times the workgroups of 64:
   // the panel update's multi-word products spread over more CUs); CLRSDP_TRSM_NC64=1 keeps 64.
   static constexpr int NB = 16, NCW = 64, NCN = 16;
+  // LDS of the LU-mode solves (modes 1 and 2) at n: launch()'s dynamic diagonal block, solved
+  // rows and panel, and the kernel's static reciprocals.  This is the size bound of the LU path.
+  static constexpr size_t lu_lds_bytes(int n) {
+    return sizeof(T) * ((size_t)NB * NB + (size_t)NB * NCW + (size_t)NB * n + NB);
+  }
   std::vector<TrsmDesc<T>> h;
   std::vector<int> t2d;
   TrsmDesc<T>* d = nullptr;
@@ -626,6 +631,14 @@ struct TrsmPlan : PlanBase {
         lds_attr_once(a64[6], (const void*)trsv_wave<T, true, NCV16, false>, (int)trsv_wave_lds<T>());
         lds_attr_once(a64[7], (const void*)trsv_wave<T, false, NCV16, false>, (int)trsv_wave_lds<T>());
       }
+    }
+    if (mode != 0 && lu_lds_bytes(nmax) > 64 * 1024) {  // (outside any graph capture)
+      if (lu_lds_bytes(nmax) > LDS_MAX)
+        throw ClrsdpError{CLRSDP_E_ARG, "LU triangular solve: matrix too large for the on-chip panel"};
+      static std::atomic<unsigned long long> alu[3];
+      lds_attr_once(alu[0], (const void*)trsm_batched<T, false, NB, NCW, 256, true, false>, (int)(LDS_MAX - 1024));
+      lds_attr_once(alu[1], (const void*)trsm_batched<T, true, NB, NCW, 256, false, true>, (int)(LDS_MAX - 1024));
+      lds_attr_once(alu[2], (const void*)trsm_batched<T, false, NB, NCW, 256, false, true>, (int)(LDS_MAX - 1024));
     }
     if (!vec_rhs())
       for (TrsmDesc<T>& t : h) { t.pad = 0; t.src = nullptr; }  // (the caller fills B)
@@ -908,10 +921,22 @@ struct MatPlan : PlanBase {  // potrf / eigmin
 };
 
 
-// pivoted LU in place (the approx_lu! / approx_inv! fallback, getrf_batched)
+// CLRSDP_LU_BLK: unset (-1) the blocked LU chain (getrf_blk_*) where getrf_batched's on-chip
+// panel does not fit; 1 the chain at every size; 0 getrf_batched only (larger matrices: E_ARG)
+inline int lu_blk_mode() {
+  const char* e = std::getenv("CLRSDP_LU_BLK");
+  return !e ? -1 : e[0] != '0' ? 1 : 0;
+}
+
+// pivoted LU in place (the approx_lu! / approx_inv! fallback): getrf_batched, one workgroup per
+// matrix, wherever its panel and U12 fit in LDS (fp64 n <= 624, dd 312, qd 156), and the blocked
+// chain across workgroups beyond (getrf_blk_panel / _swap / _update per 16-column panel, looped
+// here up to the batch's nmax: constant launch arguments, so the loop is capture-safe)
 template <class T>
 struct LuPlan : PlanBase {
-  static constexpr int NB = 16;
+  static constexpr int NB = 16, TL = 32;
+  // the static LDS of the kernels (pivot search, pivots) comes on top of the dynamic panel
+  static constexpr size_t LDS_DYN = LDS_MAX - 4096;
   std::vector<LuDesc<T>> h;
   LuDesc<T>* d = nullptr;
   int nmax = 0;
@@ -919,21 +944,56 @@ struct LuPlan : PlanBase {
     h.push_back(LuDesc<T>{A, perm, n, lda});
     nmax = std::max(nmax, n);
   }
+  static bool one_cu_fits(int n) { return getrf_lds_bytes<T, NB>(n) <= LDS_DYN; }
+  // which kernel factors matrices up to n: the chain (true) or getrf_batched; E_ARG when neither
+  static bool takes_chain(int n) {
+    const int m = lu_blk_mode();
+    if (m == 1 || (m < 0 && !one_cu_fits(n))) return true;
+    if (!one_cu_fits(n))
+      throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: matrix too large for the on-chip panel of getrf_batched (CLRSDP_LU_BLK=0)"};
+    return false;
+  }
   size_t lds = 0;
-  // (outside any graph capture: the LDS attribute is set here, not at launch)
+  bool blk = false;
+  bool panel_lds = true;  // CLRSDP_LU_PANEL_LDS=0: the chain's panel in global memory at every size
+  int* pivs = nullptr;    // the chain's pivot rows of the current panel, NB per matrix
+  // (outside any graph capture: the LDS attributes are set and the pivot scratch allocated here)
   void finalize() {
     if (h.empty()) return;
+    blk = takes_chain(nmax);
     d = own(h);
+    if (blk) {
+      pivs = own(std::vector<int>(h.size() * NB, 0));
+      panel_lds = !env_off("CLRSDP_LU_PANEL_LDS");
+      static std::atomic<unsigned long long> attr{0};
+      lds_attr_once(attr, (const void*)getrf_blk_panel<T, NB, 256>, (int)LDS_DYN);
+      return;
+    }
     lds = getrf_lds_bytes<T, NB>(nmax);
-    // the static LDS of the kernel (pivot search, pivots) comes on top of the dynamic panel
-    if (lds > LDS_MAX - 4096) throw ClrsdpError{CLRSDP_E_ARG, "LU fallback: matrix too large for the on-chip panel"};
     if (lds > 64 * 1024)
       HIPCHK(hipFuncSetAttribute((const void*)getrf_batched<T, NB, 256>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   void launch(hipStream_t s, int* info) const {
     if (h.empty()) return;
-    getrf_batched<T, NB, 256><<<(unsigned)h.size(), 256, lds, s>>>(d, info);
+    if (!blk) {
+      getrf_batched<T, NB, 256><<<(unsigned)h.size(), 256, lds, s>>>(d, info);
+      HIPCHK(hipGetLastError());
+      return;
+    }
+    const unsigned nm = (unsigned)h.size();
+    for (int k0 = 0; k0 < nmax; k0 += NB) {
+      // the panel of the largest matrix in LDS when it fits, else in place (smaller ones follow)
+      const size_t pl = sizeof(T) * (size_t)NB * (nmax - k0);
+      const bool in_lds = panel_lds && pl <= LDS_DYN;
+      getrf_blk_panel<T, NB, 256><<<nm, 256, in_lds ? pl : 0, s>>>(d, pivs, info, k0, in_lds ? 1 : 0);
+      if (nmax > NB) getrf_blk_swap<T, NB, 256><<<dim3(cdiv(nmax, 256), nm), 256, 0, s>>>(d, pivs, info, k0);
+      const int nr = nmax - k0 - NB;
+      if (nr > 0) {
+        const int ntr = (int)cdiv(nr, TL);
+        getrf_blk_update<T, NB, TL, 256><<<dim3((unsigned)(ntr * ntr), nm), 256, 0, s>>>(d, info, k0, ntr);
+      }
+    }
     HIPCHK(hipGetLastError());
   }
 };
@@ -2153,17 +2213,28 @@ struct Solver final : HandleBase {
   //   solves:  t_j = L_j^-1 rhs_j[perm_j]; u = sum_j W2_j^T t_j; dy = U_Q^-1 L_Q^-1 (p - u)[perm];
   //            dx_j = U_j^-1 (t_j + W1_j dy)                                  (MPMP.jl:1743-1776)
   //   X^-1:    X_b[perm_b] = L_b U_b; X_b^-1 = U_b^-1 L_b^-1 (P_b I)          (approx_inv!, 781)
-  // the on-chip panel of getrf_batched bounds the LU fallback (fp64 ~624, dd ~312, qd ~156)
-  bool lu_fits() const {
+  // The factorisation itself has no size bound (the blocked chain takes over beyond the on-chip
+  // panel of getrf_batched: fp64 624, dd 312, qd 156) unless CLRSDP_LU_BLK=0 keeps getrf_batched
+  // alone.  What bounds the LU path is the panel of its triangular solves (trsm_batched modes 1
+  // and 2, TrsmPlan::launch): fp64 n <= 1200, dd 560, qd 240.
+  int lu_nmax() const {
     int nmax = (int)n_y;
     for (int c = 0; c < nc(); ++c) nmax = std::max(nmax, (int)Ds[oc[c]]);
     for (const LBlk& b : lb) nmax = std::max(nmax, b.n);
-    return getrf_lds_bytes<T, LuPlan<T>::NB>(nmax) <= LDS_MAX - 4096;
+    return nmax;
+  }
+  bool lu_fits() const {
+    const int nmax = lu_nmax();
+    if (lu_blk_mode() == 0 && !LuPlan<T>::one_cu_fits(nmax)) return false;
+    return TrsmPlan<T>::lu_lds_bytes(nmax) <= LDS_MAX;
   }
   void build_lu_plans() {
     if (lu_built) return;
-    if (!lu_fits())
-      throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of getrf_batched"};
+    if (!lu_fits()) {
+      if (TrsmPlan<T>::lu_lds_bytes(lu_nmax()) > LDS_MAX)
+        throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of the LU triangular solves"};
+      throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of getrf_batched (CLRSDP_LU_BLK=0)"};
+    }
     try {
       build_lu_plans_();
     } catch (...) {  // transactional: no half-built plans or buffers survive a failure
@@ -3234,7 +3305,9 @@ struct Solver final : HandleBase {
     int add = 0;
     if ((rc == CLRSDP_E_NOT_PD_S || rc == CLRSDP_E_NOT_PD_Q) && !lu_sq()) add = CLRSDP_FACT_LU_SQ;
     else if (rc == CLRSDP_E_NOT_PD_X && !lu_x()) add = CLRSDP_FACT_LU_X;
-    if (!add || !lu_fits()) return false;  // beyond the LU panel: the reference's error stands
+    // beyond the LU solves' panel (or getrf_batched's with CLRSDP_LU_BLK=0): the reference's
+    // error stands
+    if (!add || !lu_fits()) return false;
     build_lu_plans();
     fact_flags |= add;
     drop_graphs();
@@ -3776,6 +3849,42 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
     for (int q = 0; q < W; ++q) ep[(size_t)q * nblk + b] = he[(size_t)b * W + q];
 }
 
+// Pivoted LU of each block at the word type T through LuPlan, as the solver's LU path runs it
+// (getrf_batched, or the blocked chain beyond its panel / with CLRSDP_LU_BLK=1): planes in and out
+template <class T>
+void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t* perm, int32_t* info) {
+  constexpr int W = Num<T>::W;
+  std::vector<int64_t> off(nblk + 1, 0), poff(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    off[b + 1] = off[b] + n[b] * n[b];
+    poff[b + 1] = poff[b] + n[b];
+  }
+  DeviceGuard dg(device);
+  const int64_t tot = off[nblk], np = poff[nblk];
+  std::vector<double> h((size_t)tot * W);
+  for (int64_t e = 0; e < tot; ++e)
+    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
+  DevBuf mem;
+  T* A = mem.alloc<T>(tot);
+  int* dperm = mem.alloc<int>(np);
+  int* dinfo = mem.alloc<int>(nblk);
+  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
+  LuPlan<T> lu;
+  for (int64_t b = 0; b < nblk; ++b) lu.add(A + off[b], dperm + poff[b], (int)n[b], (int)n[b]);
+  lu.finalize();
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  lu.launch(s, dinfo);
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(h.data(), A, (size_t)tot * sizeof(T), hipMemcpyDeviceToHost));
+  static_assert(sizeof(int) == sizeof(int32_t), "perm and info are 32-bit");
+  HIPCHK(hipMemcpy(perm, dperm, (size_t)np * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  for (int64_t e = 0; e < tot; ++e)
+    for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
+}
+
 int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh, const double* dMh,
                     double gamma, double* alpha, double* min_eig, std::string& err) {
   DeviceGuard dg(device);
@@ -4051,6 +4160,26 @@ int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int6
     else if (words == 2) eigmin_words<mw::dd>(device, nblocks, n, A, min_eig);
     else if (words == 4) eigmin_words<mw::qd>(device, nblocks, n, A, min_eig);
     else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n, double* A,
+                     int32_t* perm, int32_t* info) {
+  if (nblocks <= 0 || !n || !A || !perm || !info) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
+  if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  for (int64_t b = 0; b < nblocks; ++b)
+    if (n[b] <= 0 || n[b] > 4096) { g_last_error = "block size out of range"; return CLRSDP_E_ARG; }
+  try {
+    if (words == 1) getrf_words<double>(device, nblocks, n, A, perm, info);
+    else if (words == 2) getrf_words<mw::dd>(device, nblocks, n, A, perm, info);
+    else getrf_words<mw::qd>(device, nblocks, n, A, perm, info);
     return CLRSDP_OK;
   } catch (const ClrsdpError& e) {
     g_last_error = e.msg;

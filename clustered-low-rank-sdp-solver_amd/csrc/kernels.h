@@ -1939,6 +1939,225 @@ __global__ __launch_bounds__(NT) void getrf_batched(const LuDesc<T>* __restrict_
   if (tid == 0) info[blockIdx.x] = fail;
 }
 
+// ------------------------------------------------------------------------------------------
+// The same factorisation across workgroups, for matrices beyond getrf_batched's on-chip panel:
+// one chain of three launches per NB-column panel, looped on the host up to the batch's largest
+// n (LuPlan::launch).  Every element sees the operations of getrf_batched in the same order
+// (pivot rule, recip_fast of the pivot, the rank-1 updates inside the panel, the unit-lower solve
+// p = 0..q-1 and s = 0; s += L(i,q) U(q,c); a -= s in the trailing update), so the multi-word
+// factors are bitwise those of the one-CU kernel.  A matrix with n <= k0 or with its status word
+// set takes no part in a launch: info[m] stays the first failing column.
+//   getrf_blk_panel   one workgroup per matrix: rows k0..n-1 of the panel's columns, pivots to
+//                     pivs[m * NB + j] (global rows), perm updated; k0 = 0 starts perm and info
+//   getrf_blk_swap    grid (column chunks, matrices), one thread per column outside the panel:
+//                     the panel's interchanges in order, then U12 = L11^-1 A12 right of it
+//   getrf_blk_update  grid (tiles, matrices): A22 -= L21 U12 on TL x TL tiles
+// ------------------------------------------------------------------------------------------
+// (an interchange limb by limb through the members: the by-value copy of a multi-word element
+// between two generic pointers leaves a stack object behind)
+__device__ __forceinline__ void lu_swap(double& a, double& b) {
+  const double t = a;
+  a = b;
+  b = t;
+}
+__device__ __forceinline__ void lu_swap(mw::dd& a, mw::dd& b) {
+  const double a0 = a.hi, a1 = a.lo, b0 = b.hi, b1 = b.lo;
+  a.hi = b0; a.lo = b1;
+  b.hi = a0; b.lo = a1;
+}
+__device__ __forceinline__ void lu_swap(mw::qd& a, mw::qd& b) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double t = a.x[q];
+    a.x[q] = b.x[q];
+    b.x[q] = t;
+  }
+}
+// The panel's element (i, q), i counted from row k0: in LDS (ld = rows of the panel) when it fits,
+// else in place in the matrix (ld = lda; L2-resident, the workgroup's own barriers order it).
+template <class T> struct LuPanelRef {
+  T* p;
+  size_t ld;
+  __device__ __forceinline__ T& operator()(int i, int q) const { return p[(size_t)q * ld + i]; }
+};
+
+template <class T, int NB, int NT = 256>
+__global__ __launch_bounds__(NT) void getrf_blk_panel(const LuDesc<T>* __restrict__ descs,
+                                                       int* __restrict__ pivs, int* __restrict__ info,
+                                                       int k0, int in_lds) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  constexpr int NWV = NT / 64;
+  const LuDesc<T> d = descs[blockIdx.x];
+  const int n = d.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (n <= k0) return;
+  if (k0 > 0 && info[blockIdx.x] != 0) return;
+  const size_t lda = d.lda;
+  T* A = d.A;
+  int* piv = pivs + (size_t)blockIdx.x * NB;
+  __shared__ T wbest[NWV];
+  __shared__ int wrow[NWV];
+  __shared__ int prow;
+  __shared__ int fail;
+  const int nb = min(NB, n - k0), pm = n - k0;
+  T* Ak = A + k0 + (size_t)k0 * lda;
+  const LuPanelRef<T> P{in_lds ? reinterpret_cast<T*>(smem_raw) : Ak, in_lds ? (size_t)pm : lda};
+  if (tid == 0) fail = 0;
+  if (k0 == 0)
+    for (int i = tid; i < n; i += NT) d.perm[i] = i;
+  if (in_lds)
+    for (int e = tid; e < nb * pm; e += NT) {
+      const int i = e % pm, q = e / pm;
+      P(i, q) = Ak[i + (size_t)q * lda];
+    }
+  __syncthreads();
+  for (int j = 0; j < nb; ++j) {
+    // pivot: first row i >= j of maximal |P(i, j)| (ties to the smaller row), as getrf_batched
+    T best = T(-1.0);
+    int brow = pm;
+    for (int i = j + tid; i < pm; i += NT) {
+      const T a = Num<T>::abs_(P(i, j));
+      const bool gt = a > best;
+      best = sel(gt, a, best);
+      brow = gt ? i : brow;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const T ob = shfl_xor_t(best, o);
+      const int orow = __shfl_xor(brow, o);
+      const bool tk = ob > best || (!(ob < best) && orow < brow);
+      best = sel(tk, ob, best);
+      brow = tk ? orow : brow;
+    }
+    if (lane == 0) { wbest[wv] = best; wrow[wv] = brow; }
+    __syncthreads();
+    if (tid == 0) {
+      T b = wbest[0];
+      int r = wrow[0];
+      for (int w = 1; w < NWV; ++w) {
+        const T bw = wbest[w];
+        const bool tk = bw > b || (!(bw < b) && wrow[w] < r);
+        b = sel(tk, bw, b);
+        r = tk ? wrow[w] : r;
+      }
+      if (!(b > T(0.0))) {
+        fail = k0 + j + 1;
+      } else {
+        prow = r;
+        piv[j] = k0 + r;
+        const int t = d.perm[k0 + j];
+        d.perm[k0 + j] = d.perm[k0 + r];
+        d.perm[k0 + r] = t;
+      }
+    }
+    __syncthreads();
+    if (fail) break;
+    // interchange rows j and r of the panel (one thread per column), then the pivot's reciprocal
+    // by every thread (the same value as one thread's)
+    const int r0 = prow;
+    if (tid < nb && r0 != j) lu_swap(P(j, tid), P(r0, tid));
+    __syncthreads();
+    const T rp = recip_fast(P(j, j));
+    for (int i = j + 1 + tid; i < pm; i += NT) P(i, j) = P(i, j) * rp;
+    __syncthreads();
+    const int r = pm - j - 1;
+    for (int e = tid; e < r * (nb - j - 1); e += NT) {
+      const int i = j + 1 + e % r, c = j + 1 + e / r;
+      P(i, c) = P(i, c) - P(i, j) * P(j, c);
+    }
+    __syncthreads();
+  }
+  if (fail) {  // (k0 = 0 starts the status word; later panels only ever set it)
+    if (tid == 0) info[blockIdx.x] = fail;
+    return;
+  }
+  if (k0 == 0 && tid == 0) info[blockIdx.x] = 0;
+  if (in_lds)
+    for (int e = tid; e < nb * pm; e += NT) {
+      const int i = e % pm, q = e / pm;
+      Ak[i + (size_t)q * lda] = P(i, q);
+    }
+}
+
+template <class T, int NB, int NT = 256>
+__global__ __launch_bounds__(NT) void getrf_blk_swap(const LuDesc<T>* __restrict__ descs,
+                                                      const int* __restrict__ pivs,
+                                                      const int* __restrict__ info, int k0) {
+  const LuDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, tid = threadIdx.x;
+  if (n <= k0 || info[blockIdx.y] != 0) return;
+  const int nb = min(NB, n - k0), k1 = k0 + nb;
+  if ((int)blockIdx.x * NT >= n - nb) return;
+  const size_t lda = d.lda;
+  T* A = d.A;
+  __shared__ T L11[NB * NB];  // L11[p * NB + q] = L(k0 + q, k0 + p), q > p
+  __shared__ int piv[NB];
+  if (tid < nb) piv[tid] = pivs[(size_t)blockIdx.y * NB + tid];
+  for (int e = tid; e < nb * nb; e += NT) {
+    const int q = e % nb, p = e / nb;
+    if (q > p) L11[p * NB + q] = A[(k0 + q) + (size_t)(k0 + p) * lda];
+  }
+  __syncthreads();
+  const int c = blockIdx.x * NT + tid;
+  if (c >= n - nb) return;
+  const int col = c < k0 ? c : c + nb;
+  T* a = A + (size_t)col * lda;
+  for (int j = 0; j < nb; ++j) {
+    const int r = piv[j];
+    if (r != k0 + j) {
+      const T t = a[k0 + j];
+      a[k0 + j] = a[r];
+      a[r] = t;
+    }
+  }
+  if (col < k1) return;
+  // U12 = L11^-1 A12 (unit lower), the column in registers (compile-time indexed)
+  T x[NB];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    if (q < nb) {
+      T v = a[k0 + q];
+#pragma unroll
+      for (int p = 0; p < q; ++p) v = v - L11[p * NB + q] * x[p];
+      x[q] = v;
+      a[k0 + q] = v;
+    }
+  }
+}
+
+template <class T, int NB, int TL = 32, int NT = 256>
+__global__ __launch_bounds__(NT) void getrf_blk_update(const LuDesc<T>* __restrict__ descs,
+                                                        const int* __restrict__ info, int k0, int ntr) {
+  const LuDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, tid = threadIdx.x;
+  if (n <= k0 + NB || info[blockIdx.y] != 0) return;  // (n > k0 + NB: the panel is full, nb = NB)
+  const int k1 = k0 + NB, nr = n - k1;
+  const int i0 = (blockIdx.x % ntr) * TL, c0 = (blockIdx.x / ntr) * TL;
+  if (i0 >= nr || c0 >= nr) return;
+  const size_t lda = d.lda;
+  T* A = d.A;
+  __shared__ T Ls[NB * TL];  // Ls[q * TL + i] = L21(i0 + i, q)
+  __shared__ T Us[TL * NB];  // Us[c * NB + q] = U12(q, c0 + c)
+  const int ti = min(TL, nr - i0), tc = min(TL, nr - c0);
+  for (int e = tid; e < NB * TL; e += NT) {
+    const int i = e % TL, q = e / TL;
+    if (i < ti) Ls[q * TL + i] = A[(k1 + i0 + i) + (size_t)(k0 + q) * lda];
+  }
+  for (int e = tid; e < TL * NB; e += NT) {
+    const int q = e % NB, c = e / NB;
+    if (c < tc) Us[c * NB + q] = A[(k0 + q) + (size_t)(k1 + c0 + c) * lda];
+  }
+  __syncthreads();
+  for (int e = tid; e < TL * TL; e += NT) {
+    const int i = e % TL, c = e / TL;
+    if (i < ti && c < tc) {
+      T s = T(0.0);
+      for (int q = 0; q < NB; ++q) s += Ls[q * TL + i] * Us[c * NB + q];
+      T* a = A + (k1 + i0 + i) + (size_t)(k1 + c0 + c) * lda;
+      *a = *a - s;
+    }
+  }
+}
+
 // out = rows perm of in (out[i, c] = in[perm[i], c]): B_j[perms[j], :] (MPMP.jl:1463) and
 // rhs[perm] (MPMP.jl:1752, 1764).  grid (chunks, problems).  ident: in is the identity
 // (approx_inv!'s right-hand side P I).

@@ -348,6 +348,41 @@ def eigmin(blocks, precision_words: int = 1, device: int = 0):
     return from_planes(out, len(mats), w)
 
 
+def getrf(blocks, precision_words: int = 1, device: int = 0, raw_limbs: bool = False):
+    """Partially pivoted LU of each square block, ``A[perm] = L U``, at fp64 / double-double /
+    quad-double (clrsdp_getrf: approx_lu!, MPMP.jl:1436, 1501, as the solver's LU path runs it).
+    Blocks are float arrays or object arrays of mpmath numbers (split exactly into limbs).
+    Returns ``(LU, perms, info)``: per block the factors in one matrix (L unit, below the
+    diagonal; U on and above it; floats at words 1, else the exact limb sums as mpmath numbers),
+    ``perm[k]`` = original row at position k (0-based), and ``info`` = 0 or the 1-based column
+    of the first zero pivot.  With ``raw_limbs`` the factors come back as the raw limbs instead,
+    one float array of shape (words, n, n) per block."""
+    w = int(precision_words)
+    mats = [np.asarray(b) for b in blocks]
+    for a in mats:
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("blocks must be square")
+    n = np.array([a.shape[0] for a in mats], dtype=np.int64)
+    flat = np.concatenate([a.reshape(-1, order="F") for a in mats]) if mats else np.zeros(0)
+    planes = np.ascontiguousarray(to_planes(flat, w), dtype=np.float64).copy()
+    perm = np.zeros(max(int(n.sum()), 1), dtype=np.int32)
+    info = np.zeros(max(len(mats), 1), dtype=np.int32)
+    _lib.check(_lib.lib().clrsdp_getrf(device, w, len(mats), n.ctypes.data_as(_lib.P_i64),
+                                       _ptr(planes), perm.ctypes.data_as(_lib.P_i32),
+                                       info.ctypes.data_as(_lib.P_i32)))
+    off = np.concatenate([[0], np.cumsum(n * n)])
+    poff = np.concatenate([[0], np.cumsum(n)])
+    if raw_limbs:
+        P = planes.reshape(w, -1)
+        LU = [P[:, off[b]:off[b + 1]].reshape((w, n[b], n[b])).transpose(0, 2, 1).copy()
+              for b in range(len(mats))]
+    else:
+        vals = planes if w == 1 else from_planes(planes, flat.size, w)
+        LU = [vals[off[b]:off[b + 1]].reshape((n[b], n[b]), order="F") for b in range(len(mats))]
+    perms = [perm[poff[b]:poff[b + 1]].copy() for b in range(len(mats))]
+    return LU, perms, info[:len(mats)].copy()
+
+
 def initial_point(bi: BlockInfo, omega_p, omega_d):
     """x = 0, X = omega_p I, y = 0, Y = omega_d I (MPMP.jl:660-686)."""
     x = np.zeros(sum(bi.dim_S))

@@ -326,6 +326,14 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                       const double* A, double* min_eig);
 
+/* Partially pivoted LU of each block in place, A_b[perm_b] = L_b U_b (approx_lu!, MPMP.jl:1436,
+ * 1501; the factor of approx_inv!, 781), as the solver's LU path runs it.  A: nblocks blocks of
+ * sizes n[] concatenated column-major as `words` planes; on return L (unit, below the diagonal)
+ * and U.  perm: sum n[] entries, perm_b[k] = original row at position k (0-based).  info: nblocks,
+ * 0 or the 1-based column of the first zero pivot. */
+int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
+                     double* A, int32_t* perm, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif
