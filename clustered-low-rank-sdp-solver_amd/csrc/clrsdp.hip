@@ -144,10 +144,30 @@ inline void lds_attr_once(std::atomic<unsigned long long>& seen, const void* fn,
 // --------------------------------------------------------------------------------------------
 // launch plans: descriptor arrays built once at creation, replayed every iteration
 // --------------------------------------------------------------------------------------------
-// register-tile shapes of chol_inv_reg per word type (NMAX = TR * GR)
-template <class T> struct RegCfg { static constexpr int TR = 4, TC = 8, GR = 32, GC = 16; };
-template <> struct RegCfg<dd> { static constexpr int TR = 1, TC = 4, GR = 64, GC = 16; };  // 1024 threads
-template <> struct RegCfg<qd> { static constexpr int TR = 1, TC = 1, GR = 32, GC = 32; };  // 1024 threads
+// a development switch is on when set to anything but a value starting with '0' (so that
+// NAME=0 switches it off again, for every switch alike)
+static inline bool env_on(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] != '0';
+}
+// a default-on switch is off only when set to a value starting with '0'
+static inline bool env_off(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '0';
+}
+// an integer switch: `dflt` when unset, else the decimal number its value starts with (0 when it
+// starts with none); *exact, when given, tells whether the whole value was that number
+static inline long env_int(const char* name, long dflt, bool* exact = nullptr) {
+  const char* e = std::getenv(name);
+  if (exact) *exact = true;
+  if (!e) return dflt;
+  char* end = nullptr;
+  const long v = std::strtol(e, &end, 10);
+  if (exact) *exact = end != e && *end == '\0';
+  return v;
+}
+// (DESIGN.md §13 lists every switch read here, and the retired ones with their measurements)
+
 // chol_lookahead's switches (CLRSDP_LA_OPTS, kernels_dense.h).  Default 2: one Newton step for
 // the quad-double pivot reciprocal (~2^-208 relative; the second step was a third of the chain:
 // C5 879 -> 930 it/s, round 5 A/B); bit 0 (chain priority) measured nothing
@@ -155,47 +175,20 @@ template <> struct RegCfg<qd> { static constexpr int TR = 1, TC = 1, GR = 32, GC
 // rejected with a message and the default kept.
 inline int la_opts() {
   static const int o = [] {
-    const char* e = std::getenv("CLRSDP_LA_OPTS");
-    if (!e) return 2;
-    char* end = nullptr;
-    const long v = std::strtol(e, &end, 10);
-    if (end == e || *end != '\0' || v < 0 || (v & ~3L)) {
-      std::fprintf(stderr, "clrsdp: CLRSDP_LA_OPTS=%s ignored (bits 0 and 1 only); using 2\n", e);
+    bool exact = true;
+    const long v = env_int("CLRSDP_LA_OPTS", 2, &exact);
+    if (!exact || v < 0 || (v & ~3L)) {
+      std::fprintf(stderr, "clrsdp: CLRSDP_LA_OPTS ignored (a number with bits 0 and 1 only); using 2\n");
       return 2;
     }
     return (int)v;
   }();
   return o;
 }
-template <class T> constexpr int reg_nmax() { return std::is_same<T, double>::value ? 128 : RegCfg<T>::TR * RegCfg<T>::GR; }
-// multi-word blocks n <= 64 factor with chol_packed (liveness-packed slots, bitwise the same
-// factors as chol_inv_reg); CLRSDP_CHOL_PACKED=0 keeps the tile grid (A/B)
-inline bool chol_packed_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("CLRSDP_CHOL_PACKED");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// quad-double factors in the square-root-free form (chol_packed LDL); CLRSDP_CHOL_LDL=0: LL^T
-inline bool chol_ldl_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("CLRSDP_CHOL_LDL");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-template <class T, bool INV, int NMAX = 64>
-void launch_chol_packed(unsigned nb, hipStream_t s, const MatDesc<T>* in, const MatDesc<T>* oi,
-                        const MatDesc<T>* ol, int* info) {
-  constexpr int NT = 1024;
-  if constexpr (std::is_same<T, mw::qd>::value) {
-    if (chol_ldl_on()) {
-      chol_packed<T, NT, INV, true, NMAX><<<nb, NT, 0, s>>>(in, oi, ol, info);
-      return;
-    }
-  }
-  chol_packed<T, NT, INV, false, NMAX><<<nb, NT, 0, s>>>(in, oi, ol, info);
+// the largest block of the on-chip factorisation path (L^-1 and products instead of solves):
+// chol_inv_tiles (fp64) and chol_lookahead with the inverse (multi-word)
+template <class T> constexpr int reg_nmax() {
+  return std::is_same<T, double>::value ? 128 : std::is_same<T, dd>::value ? 64 : 32;
 }
 // eigmin_lds: A (n^2), v, NC = 8 (n <= 64) or 4 partial vectors, dg, e2, w, scalars
 template <class T> size_t eig_lds_bytes(int n) {
@@ -212,18 +205,6 @@ inline std::vector<TileRef> tile_major(const std::vector<int>& ntiles) {
     for (size_t p = 0; p < ntiles.size(); ++p)
       if (t < ntiles[p]) out.push_back(TileRef{(int)p, t});
   return out;
-}
-
-// a development switch is on when set to anything but a value starting with '0' (so that
-// NAME=0 switches it off again, for every switch alike)
-static inline bool env_on(const char* name) {
-  const char* e = std::getenv(name);
-  return e && e[0] != '0';
-}
-// a default-on switch is off only when set to a value starting with '0'
-static inline bool env_off(const char* name) {
-  const char* e = std::getenv(name);
-  return e && e[0] == '0';
 }
 
 // work enqueued on another stream for one scope: `stream` is restored when the scope ends,
@@ -264,9 +245,8 @@ struct GemmPlan : PlanBase {
   std::vector<TileRef> t2d;
   GemmDesc<T>* d = nullptr;
   TileRef* dt = nullptr;
-  // gemm_f64_lds (fp64) and gemm_valu_ks (multi-word; CLRSDP_GEMM_VALU16=1: gemm_valu) output
-  // tiles, fixed when the plan is created
-  const int TILE = std::is_same<T, double>::value ? 64 : env_on("CLRSDP_GEMM_VALU16") ? 16 : 8;
+  // gemm_f64_lds (fp64) and gemm_valu_ks (multi-word) output tiles
+  static constexpr int TILE = std::is_same<T, double>::value ? 64 : 8;
 
   void clear() {  // back to an empty plan (a failed build_lu_plans)
     h.clear();
@@ -314,9 +294,6 @@ struct GemmPlan : PlanBase {
   // sym: every problem square with an exactly symmetric result wanted (gemm_f64_lds SYM: the
   // lower tiles only, each written with its mirror image); fp64, beta = 0
   bool sym = false;
-  // prio: raised wave priority for a critical-path batch that runs beside side-stream work
-  // (gemm_f64_uni / gemm_f64_dyn; set before finalize)
-  bool prio = false;
   // upper (multi-word, round 6): every problem square with a symmetric product of which only the
   // tiles on and above the diagonal are wanted (the Schur pairings V^T X^-1 V, V^T Y V of m = 1
   // blocks: schur_assemble reads (min, max)); the launch lists those tiles only -- half the
@@ -356,22 +333,18 @@ struct GemmPlan : PlanBase {
     } else {
       t2d = tile_major(ntiles);
     }
-    if (prio && dyn)
-      for (auto& g : h) g.flags |= 8;
     d = own(h);
     dt = own(t2d);
     detect_uniform();
-    ug.prio = prio ? 1 : 0;
   }
   // fp64 batches of one shape at constant operand strides take gemm_f64_uni (no descriptor
-  // chain before the first operand load); CLRSDP_NO_UNI_GEMM keeps the descriptor kernels
+  // chain before the first operand load)
   bool uni = false;
   int uts = 64;  // gemm_f64_uni output tile (64 or 32)
   UniGemm ug{};
   void detect_uniform() {
     if constexpr (std::is_same<T, double>::value) {
-      static const bool off = env_on("CLRSDP_NO_UNI_GEMM");
-      if (off || gemv || dyn || h.empty()) return;
+      if (gemv || dyn || h.empty()) return;
       const GemmDesc<T>& g0 = h[0];
       auto stride = [&](auto get, long long& st) {
         st = h.size() > 1 ? (long long)(get(h[1]) - get(h[0])) : 0;
@@ -400,8 +373,7 @@ struct GemmPlan : PlanBase {
       // tile is then latency-bound, ~9.4 us for a 128^3 product against 6.5 us split over four
       // CUs, tools/micro/gemm_tiles.hip); CLRSDP_GEMM_TS32_BELOW sets the threshold (tiles)
       // (read at every plan build, so a test can force either tile in one process)
-      const char* e32 = std::getenv("CLRSDP_GEMM_TS32_BELOW");
-      const long ts32_below = e32 ? std::atol(e32) : 192L;
+      const long ts32_below = env_int("CLRSDP_GEMM_TS32_BELOW", 192L);
       const long t64m = (long)cdiv(g0.M, 64), t64n = (long)cdiv(g0.N, 64);
       const long tiles64 = u.P * (sym ? t64m * (t64m + 1) / 2 : t64m * t64n);
       uts = tiles64 < ts32_below ? 32 : 64;
@@ -425,19 +397,11 @@ struct GemmPlan : PlanBase {
       throw ClrsdpError{CLRSDP_E_ARG, "fused diagonal epilogue is fp64 only"};
     const unsigned grid = (unsigned)t2d.size();
     if (gemv) {  // (tb only with K = 1: B[0] is the vector either way)
-      // fp64: deep load pipelines (CLRSDP_GEMV_DEEP=0: the 8-deep round-4 loops)
-      // (multi-word, transposed: DEEP selects the thread-per-column form, the quad-double default
-      // -- C5 936 -> 977 it/s; double-double keeps the 16-lane reduction form, 834 against 820
-      // with the column form -- CLRSDP_GEMV_MW_T16=1 / CLRSDP_GEMV_MW_COL=1 swap them; round 5)
-      static const bool deep = !env_off("CLRSDP_GEMV_DEEP");
-      static const bool mw_t16 = env_on("CLRSDP_GEMV_MW_T16"), mw_col = env_on("CLRSDP_GEMV_MW_COL");
-      const bool deep_t = std::is_same<T, double>::value ? deep
-                          : std::is_same<T, mw::qd>::value ? !mw_t16
-                                                           : mw_col;
-      if (ta && deep_t) gemv_batched<T, true><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else if (ta) gemv_batched<T, true, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else if (deep) gemv_batched<T, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else gemv_batched<T, false, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
+      // the transposed product: DEEP is the deep load pipeline (fp64) and the thread-per-column
+      // form (quad-double); double-double keeps the 16-lane reduction form
+      constexpr bool deep_t = !std::is_same<T, mw::dd>::value;
+      if (ta) gemv_batched<T, true, deep_t><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
+      else gemv_batched<T, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -471,16 +435,11 @@ struct GemmPlan : PlanBase {
       else if (ta && !tb) gemm_f64_lds<true, false><<<grid, 512, 0, s>>>(d, dt, alpha, beta, ds, dmult);
       else if (!ta && tb) gemm_f64_lds<false, true><<<grid, 512, 0, s>>>(d, dt, alpha, beta, ds, dmult);
       else gemm_f64_lds<true, true><<<grid, 512, 0, s>>>(d, dt, alpha, beta, ds, dmult);
-    } else if (TILE == 8) {
+    } else {
       if (!ta && !tb) gemm_valu_ks<T, false, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
       else if (ta && !tb) gemm_valu_ks<T, true, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
       else if (!ta && tb) gemm_valu_ks<T, false, true><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
       else gemm_valu_ks<T, true, true><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-    } else {
-      if (!ta && !tb) gemm_valu<T, false, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else if (ta && !tb) gemm_valu<T, true, false><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else if (!ta && tb) gemm_valu<T, false, true><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
-      else gemm_valu<T, true, true><<<grid, 256, 0, s>>>(d, dt, alpha, beta);
     }
     HIPCHK(hipGetLastError());
   }
@@ -520,26 +479,26 @@ struct ChainPlan {
   }
 };
 
-template <bool DB, int TS>
-void launch_uni_db(const UniGemm& u, hipStream_t s, bool ta, bool tb, bool sca, bool sym, int tag,
+template <int TS>
+void launch_uni_ts(const UniGemm& u, hipStream_t s, bool ta, bool tb, bool sca, bool sym, int tag,
                    unsigned long long* stamp, double alpha, double beta, const double* ds, double dmult) {
   constexpr int NW = TS == 64 ? 8 : 2, NT = 64 * NW;
   const unsigned tiles = (unsigned)(u.P * (int)cdiv(u.M, TS) * u.tn);
   if (sca) {
-    gemm_f64_uni<false, true, 0, 32, NW, false, true, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
+    gemm_f64_uni<false, true, 0, 32, NW, false, true, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
   } else if (sym) {
     if (beta != 0.0 || ds) throw ClrsdpError{CLRSDP_E_ARG, "symmetric GEMM epilogue: beta = 0 only"};
     const unsigned grid = (unsigned)(u.P * u.tsym);
-    if (!ta && tb) gemm_f64_uni<false, true, 0, 32, NW, true, false, DB, TS><<<grid, NT, 0, s>>>(u, alpha, 0.0);
-    else if (!ta && !tb) gemm_f64_uni<false, false, 0, 32, NW, true, false, DB, TS><<<grid, NT, 0, s>>>(u, alpha, 0.0);
+    if (!ta && tb) gemm_f64_uni<false, true, 0, 32, NW, true, false, true, TS><<<grid, NT, 0, s>>>(u, alpha, 0.0);
+    else if (!ta && !tb) gemm_f64_uni<false, false, 0, 32, NW, true, false, true, TS><<<grid, NT, 0, s>>>(u, alpha, 0.0);
     else throw ClrsdpError{CLRSDP_E_ARG, "symmetric GEMM epilogue: op(A) = A only"};
   } else {
-    if (tag == 1 && !ta && tb) gemm_f64_uni<false, true, 1, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult, stamp);
-    else if (tag == 3 && !ta && tb) gemm_f64_uni<false, true, 3, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult, stamp);
-    else if (!ta && !tb) gemm_f64_uni<false, false, 0, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
-    else if (ta && !tb) gemm_f64_uni<true, false, 0, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
-    else if (!ta && tb) gemm_f64_uni<false, true, 0, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
-    else gemm_f64_uni<true, true, 0, 32, NW, false, false, DB, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
+    if (tag == 1 && !ta && tb) gemm_f64_uni<false, true, 1, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult, stamp);
+    else if (tag == 3 && !ta && tb) gemm_f64_uni<false, true, 3, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult, stamp);
+    else if (!ta && !tb) gemm_f64_uni<false, false, 0, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
+    else if (ta && !tb) gemm_f64_uni<true, false, 0, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
+    else if (!ta && tb) gemm_f64_uni<false, true, 0, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
+    else gemm_f64_uni<true, true, 0, 32, NW, false, false, true, TS><<<tiles, NT, 0, s>>>(u, alpha, beta, ds, dmult);
   }
   HIPCHK(hipGetLastError());
 }
@@ -548,14 +507,8 @@ template <class T>
 template <class U>
 void GemmPlan<T>::launch_uni_impl(hipStream_t s, double alpha, double beta, const double* ds, double dmult) const {
   if constexpr (std::is_same<T, double>::value) {
-    // CLRSDP_UNI_DB=0: single-buffered slabs (two barriers per k-step), for A/B timing
-    static const bool db = [] {
-      const char* e = std::getenv("CLRSDP_UNI_DB");
-      return !(e && e[0] == '0');
-    }();
-    if (uts == 32) launch_uni_db<true, 32>(ug, s, ta, tb, sca, sym, tag, stamp, alpha, beta, ds, dmult);
-    else if (db) launch_uni_db<true, 64>(ug, s, ta, tb, sca, sym, tag, stamp, alpha, beta, ds, dmult);
-    else launch_uni_db<false, 64>(ug, s, ta, tb, sca, sym, tag, stamp, alpha, beta, ds, dmult);
+    if (uts == 32) launch_uni_ts<32>(ug, s, ta, tb, sca, sym, tag, stamp, alpha, beta, ds, dmult);
+    else launch_uni_ts<64>(ug, s, ta, tb, sca, sym, tag, stamp, alpha, beta, ds, dmult);
   }
 }
 
@@ -563,7 +516,7 @@ template <class T>
 struct TrsmPlan : PlanBase {
   // NC: right-hand sides per workgroup.  Multi-word solves with many right-hand sides
   // (W = L^-1 B) take 16 (one diagonal pass of 256 threads, and four times the workgroups of 64:
-  // the panel update's multi-word products spread over more CUs); CLRSDP_TRSM_NC64=1 keeps 64.
+  // the panel update's multi-word products spread over more CUs).
   static constexpr int NB = 16, NCW = 64, NCN = 16;
   // LDS of the LU-mode solves (modes 1 and 2) at n: launch()'s dynamic diagonal block, solved
   // rows and panel, and the kernel's static reciprocals.  This is the size bound of the LU path.
@@ -576,9 +529,10 @@ struct TrsmPlan : PlanBase {
   int* dt = nullptr;
   int nmax = 0, rmax = 0;
   bool narrow = false;
-  // multi-word solves with n <= 64: trsv_wave, one wave per right-hand side, 4 waves per
-  // workgroup for vector solves and 16 (four per SIMD, their chains interleaved; one LDS copy of
-  // L per 16 right-hand sides) for W_j = L_j^-1 B_j (CLRSDP_TRSV_BLOCKED=1 keeps trsm_batched)
+  // multi-word solves with n <= 128: trsv_wave (n <= 64) / trsv_wave128 (L through LDS in
+  // 32-step chunks), one wave per right-hand side, 4 waves per workgroup for vector solves and 16
+  // (four per SIMD, their chains interleaved; one LDS copy of L per 16 right-hand sides) for
+  // W_j = L_j^-1 B_j; trsm_batched beyond
   static constexpr int NCV = 4, NCV16 = 16;
   bool vec = false;
   int ncv = NCV;
@@ -600,36 +554,21 @@ struct TrsmPlan : PlanBase {
   }
   void finalize() {
     if (h.empty()) return;
-    narrow = mode == 0 && !std::is_same<T, double>::value && rmax >= 32 && !env_on("CLRSDP_TRSM_NC64");
-    // (64 < n <= 128: trsv_wave128, L through LDS in 32-step chunks; CLRSDP_TRSV128=0 keeps
-    // trsm_batched there)
-    const char* e128 = std::getenv("CLRSDP_TRSV128");
-    vec = mode == 0 && !std::is_same<T, double>::value && !env_on("CLRSDP_TRSV_BLOCKED") &&
-          (nmax <= 64 || (nmax <= 128 && !(e128 && e128[0] == '0')));
-    // (CLRSDP_TRSV_NW4=1: four right-hand sides per workgroup whatever their number: one chain
-    // per SIMD, more workgroups)
-    static const bool nw4 = env_on("CLRSDP_TRSV_NW4");
-    ncv = (rmax <= NCV || nw4 || four) ? NCV : NCV16;
+    narrow = mode == 0 && !std::is_same<T, double>::value && rmax >= 32;
+    vec = mode == 0 && !std::is_same<T, double>::value && nmax <= 128;
+    ncv = (rmax <= NCV || four) ? NCV : NCV16;
     const int nc = vec ? ncv : narrow ? NCN : NCW;
     if constexpr (!std::is_same<T, double>::value) {
       if (vec) {  // (outside any graph capture)
-        static std::atomic<unsigned long long> a128[8], a64[8];
+        static std::atomic<unsigned long long> a128[4], a64[4];
         lds_attr_once(a128[0], (const void*)trsv_wave128<T, true, NCV>, (int)trsv_wave128_lds<T>());
         lds_attr_once(a128[1], (const void*)trsv_wave128<T, false, NCV>, (int)trsv_wave128_lds<T>());
         lds_attr_once(a128[2], (const void*)trsv_wave128<T, true, NCV16>, (int)trsv_wave128_lds<T>());
         lds_attr_once(a128[3], (const void*)trsv_wave128<T, false, NCV16>, (int)trsv_wave128_lds<T>());
-        lds_attr_once(a128[4], (const void*)trsv_wave128<T, true, NCV, false>, (int)trsv_wave128_lds<T>());
-        lds_attr_once(a128[5], (const void*)trsv_wave128<T, false, NCV, false>, (int)trsv_wave128_lds<T>());
-        lds_attr_once(a128[6], (const void*)trsv_wave128<T, true, NCV16, false>, (int)trsv_wave128_lds<T>());
-        lds_attr_once(a128[7], (const void*)trsv_wave128<T, false, NCV16, false>, (int)trsv_wave128_lds<T>());
         lds_attr_once(a64[0], (const void*)trsv_wave<T, true, NCV>, (int)trsv_wave_lds<T>());
         lds_attr_once(a64[1], (const void*)trsv_wave<T, false, NCV>, (int)trsv_wave_lds<T>());
         lds_attr_once(a64[2], (const void*)trsv_wave<T, true, NCV16>, (int)trsv_wave_lds<T>());
         lds_attr_once(a64[3], (const void*)trsv_wave<T, false, NCV16>, (int)trsv_wave_lds<T>());
-        lds_attr_once(a64[4], (const void*)trsv_wave<T, true, NCV, false>, (int)trsv_wave_lds<T>());
-        lds_attr_once(a64[5], (const void*)trsv_wave<T, false, NCV, false>, (int)trsv_wave_lds<T>());
-        lds_attr_once(a64[6], (const void*)trsv_wave<T, true, NCV16, false>, (int)trsv_wave_lds<T>());
-        lds_attr_once(a64[7], (const void*)trsv_wave<T, false, NCV16, false>, (int)trsv_wave_lds<T>());
       }
     }
     if (mode != 0 && lu_lds_bytes(nmax) > 64 * 1024) {  // (outside any graph capture)
@@ -650,33 +589,28 @@ struct TrsmPlan : PlanBase {
     d = own(h);
     dt = own(t2d);
   }
-  template <bool PF>
   void launch_vec(hipStream_t s, bool trans, unsigned grid) const {
     if constexpr (!std::is_same<T, double>::value) {
       if (nmax > 64) {
         const size_t l = trsv_wave128_lds<T>();
         if (ncv == NCV16) {
-          if (trans) trsv_wave128<T, true, NCV16, PF><<<grid, 64 * NCV16, l, s>>>(d, dt);
-          else trsv_wave128<T, false, NCV16, PF><<<grid, 64 * NCV16, l, s>>>(d, dt);
+          if (trans) trsv_wave128<T, true, NCV16><<<grid, 64 * NCV16, l, s>>>(d, dt);
+          else trsv_wave128<T, false, NCV16><<<grid, 64 * NCV16, l, s>>>(d, dt);
         } else {
-          if (trans) trsv_wave128<T, true, NCV, PF><<<grid, 64 * NCV, l, s>>>(d, dt);
-          else trsv_wave128<T, false, NCV, PF><<<grid, 64 * NCV, l, s>>>(d, dt);
+          if (trans) trsv_wave128<T, true, NCV><<<grid, 64 * NCV, l, s>>>(d, dt);
+          else trsv_wave128<T, false, NCV><<<grid, 64 * NCV, l, s>>>(d, dt);
         }
       } else if (ncv == NCV16) {
-        if (trans) trsv_wave<T, true, NCV16, PF><<<grid, 64 * NCV16, trsv_wave_lds<T>(), s>>>(d, dt);
-        else trsv_wave<T, false, NCV16, PF><<<grid, 64 * NCV16, trsv_wave_lds<T>(), s>>>(d, dt);
+        if (trans) trsv_wave<T, true, NCV16><<<grid, 64 * NCV16, trsv_wave_lds<T>(), s>>>(d, dt);
+        else trsv_wave<T, false, NCV16><<<grid, 64 * NCV16, trsv_wave_lds<T>(), s>>>(d, dt);
       } else {
-        if (trans) trsv_wave<T, true, NCV, PF><<<grid, 64 * NCV, trsv_wave_lds<T>(), s>>>(d, dt);
-        else trsv_wave<T, false, NCV, PF><<<grid, 64 * NCV, trsv_wave_lds<T>(), s>>>(d, dt);
+        if (trans) trsv_wave<T, true, NCV><<<grid, 64 * NCV, trsv_wave_lds<T>(), s>>>(d, dt);
+        else trsv_wave<T, false, NCV><<<grid, 64 * NCV, trsv_wave_lds<T>(), s>>>(d, dt);
       }
     }
   }
   // the vector-solve kernels take the identity / a separate source as right-hand sides
-  // (CLRSDP_TRSV_RHS=0: the caller copies them into B, as before round 6)
-  bool vec_rhs() const {
-    static const bool on = !env_off("CLRSDP_TRSV_RHS");
-    return on && vec && mode == 0 && !std::is_same<T, double>::value;
-  }
+  bool vec_rhs() const { return vec; }
   // mode (the LU fallback's factors): 0 = potrf's L; 1 = unit lower L of getrf; 2 = getrf's U,
   // read transposed (forward: U^T x = b; trans: U x = b)
   int mode = 0;
@@ -687,10 +621,7 @@ struct TrsmPlan : PlanBase {
     const unsigned grid = (unsigned)t2d.size();
     if constexpr (!std::is_same<T, double>::value) {
       if (vec && mode == 0) {
-        // (CLRSDP_TRSV_PF=0: the staging loops that wait on each load of L in turn)
-        static const bool pf = !env_off("CLRSDP_TRSV_PF");
-        if (pf) launch_vec<true>(s, trans, grid);
-        else launch_vec<false>(s, trans, grid);
+        launch_vec(s, trans, grid);
         HIPCHK(hipGetLastError());
         return;
       }
@@ -739,12 +670,11 @@ struct MatPlan : PlanBase {  // potrf / eigmin
     h.push_back(m);
     nmax = std::max(nmax, n);
   }
-  // multi-word Cholesky factors of blocks with n <= 128: the register-resident chol_packed
-  // without the inverse (1024 threads, the whole block on chip, two barriers per column) writes
-  // L in place -- against potrf_batched's 16-column panels with a serial pivot chain (n <= 64
-  // falls back to chol_inv_reg with CLRSDP_CHOL_PACKED=0).  Set before finalize();
-  // CLRSDP_REG_POTRF=0 keeps potrf_batched.
-  bool reg_potrf = false;
+  // multi-word Cholesky factors on one CU: chol_lookahead without the inverse (1024 threads, the
+  // whole block on chip, the pivot chain beside the trailing update) writes L in place, up to
+  // n = 128 (double-double) or 64 (quad-double: a 128 instance would spill) -- against
+  // potrf_batched's 16-column panels with a serial pivot chain beyond.
+  static constexpr int LA_NMAX = std::is_same<T, mw::dd>::value ? 128 : 64;
   int* redo = nullptr;  // eigmin_mx's per-block fallback flags
   // blocked multi-word potrf across workgroups (potrf_blk_*, kernels_dense.h; round 6): taken
   // for the double-double blocks above 64 (CLRSDP_POTRF_BLK=0 keeps chol_lookahead there).
@@ -767,12 +697,6 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       }
     }
     if (!std::is_same<T, double>::value) redo = own(std::vector<int>(h.size(), 1));
-    const char* e = std::getenv("CLRSDP_REG_POTRF");
-    // (double-double blocks 65..128: chol_packed only, CLRSDP_CHOL_PACKED128=0 keeps
-    // potrf_batched there; quad-double would spill at nine slots per thread)
-    const char* e2 = std::getenv("CLRSDP_CHOL_PACKED128");
-    const int lim = std::is_same<T, mw::dd>::value && chol_packed_on() && !(e2 && e2[0] == '0') ? 128 : 64;
-    reg_potrf = reg_potrf && !std::is_same<T, double>::value && nmax <= lim && !(e && e[0] == '0');
   }
   void potrf(hipStream_t s, int* info) const {
     if (h.empty()) return;
@@ -793,38 +717,16 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       }
     }
     if constexpr (!std::is_same<T, double>::value) {
-      // the look-ahead potrf (chol_lookahead: the pivot chain beside the trailing update);
-      // CLRSDP_CHOL_LA=0 keeps chol_packed.  At n <= 64 the bulk waves on the chain's SIMD stay
-      // idle (SKIP0, round 6: qd n = 51 138 -> 126 us, dd n = 64 63 -> 61 us)
-      static const bool la = !env_off("CLRSDP_CHOL_LA");
-      if (reg_potrf && la && nmax <= (std::is_same<T, mw::dd>::value ? 128 : 64)) {
-        bool done = false;
-        if constexpr (std::is_same<T, mw::dd>::value) {  // (no quad-double instance: it would spill)
-          if (nmax > 64) {
-            chol_lookahead<T, false, false, 128><<<(unsigned)h.size(), 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-            done = true;
-          }
-        }
-        if (done) {
-        } else if (std::is_same<T, mw::qd>::value && chol_ldl_on())
-          chol_lookahead<T, false, true, 64, 15, true><<<(unsigned)h.size(), 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-        else
-          chol_lookahead<T, false, false, 64, 15, true><<<(unsigned)h.size(), 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-        HIPCHK(hipGetLastError());
-        return;
-      }
-      if (reg_potrf) {
+      if (nmax <= LA_NMAX) {
+        // at n <= 64 the bulk waves on the chain's SIMD stay idle (SKIP0, round 6: qd n = 51
+        // 138 -> 126 us, dd n = 64 63 -> 61 us); quad-double in the square-root-free LDL form
+        const unsigned nm = (unsigned)h.size();
         if constexpr (std::is_same<T, mw::dd>::value) {
-          if (nmax > 64) {
-            chol_packed<T, 1024, false, false, 128><<<(unsigned)h.size(), 1024, 0, s>>>(d, d, d, info);
-            HIPCHK(hipGetLastError());
-            return;
-          }
+          if (nmax > 64) chol_lookahead<T, false, false, 128><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
+          else chol_lookahead<T, false, false, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
+        } else {
+          chol_lookahead<T, false, true, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
         }
-        if (chol_packed_on())
-          launch_chol_packed<T, false>((unsigned)h.size(), s, d, d, d, info);
-        else
-          chol_inv_reg<T, 1, 4, 64, 16, false><<<(unsigned)h.size(), 1024, 0, s>>>(d, d, d, info);
         HIPCHK(hipGetLastError());
         return;
       }
@@ -840,37 +742,18 @@ struct MatPlan : PlanBase {  // potrf / eigmin
     if (h.empty()) return;
     if constexpr (std::is_same<T, double>::value) {
       if (nmax <= 128) {  // matrix in registers
-        // eigmin_split (round 4: one reflector chain wave + 8 bulk waves) unless
-        // CLRSDP_EIG_REG=1 (eigmin_reg: every live wave builds the reflector)
-        static const bool reg = env_on("CLRSDP_EIG_REG");
-        // the last 24 columns on the chain wave alone (no barriers): 144.0 against 147.4 us per
-        // batch of 128 blocks of 128, bitwise the same lambda_min on 1048 of 1056 test blocks
-        // (tools/micro/eig_split_bench.hip); CLRSDP_EIG_TAIL=0 keeps the two-barrier loop
-        static const bool etail = !env_off("CLRSDP_EIG_TAIL");
-        // (round 6: eigmin_onebar, one barrier per column with the next reflector's
-        // matrix-vector product under the chain's reflector, measured 203 against 143 us per
-        // batch of 128 blocks of 128 -- the bulk waves are VALU-issue bound -- and stays a
-        // microbenchmark, tools/micro/eig_onebar_bench.hip)
-        if (reg) eigmin_reg<<<(unsigned)h.size(), 512, 0, s>>>(d, out);
-        else if (etail) eigmin_split<0, 24><<<(unsigned)h.size(), 576, 0, s>>>(d, out);
-        else eigmin_split<0><<<(unsigned)h.size(), 576, 0, s>>>(d, out);
+        // eigmin_split: one reflector chain wave + 8 bulk waves, the last 24 columns on the
+        // chain wave alone (no barriers)
+        eigmin_split<0, 24><<<(unsigned)h.size(), 576, 0, s>>>(d, out);
         HIPCHK(hipGetLastError());
         return;
       }
     }
-    // CLRSDP_EIG_NEWTON=0 keeps the multi-word multisection from the fp64 bracket (A/B)
-    static const bool newton = [] {
-      const char* e = std::getenv("CLRSDP_EIG_NEWTON");
-      return !(e && e[0] == '0');
-    }();
     // multi-word, n <= 64: an fp64 eigenpair refined at the word's width (eigmin_mx; the blocks
     // it cannot certify go to eigmin_lds2 in a second, flagged launch) unless CLRSDP_EIG_MX=0
-    static const bool mx = [] {
-      const char* e = std::getenv("CLRSDP_EIG_MX");
-      return !(e && e[0] == '0');
-    }();
+    static const bool mx = !env_off("CLRSDP_EIG_MX");
     if constexpr (!std::is_same<T, double>::value) {
-      if (mx && newton && redo && nmax <= 64 && eigmx_lds_bytes<T>(nmax) + EIGMX_STATIC_LDS <= LDS_MAX &&
+      if (mx && redo && nmax <= 64 && eigmx_lds_bytes<T>(nmax) + EIGMX_STATIC_LDS <= LDS_MAX &&
           eig2_lds_bytes<T>(nmax) <= LDS_MAX && (sizeof(T) <= 16 || nmax <= 64)) {
         static std::atomic<unsigned long long> attrm{0}, attr2r{0};
         static const bool dbg = env_on("CLRSDP_EIGMX_STATS");
@@ -884,34 +767,26 @@ struct MatPlan : PlanBase {  // potrf / eigmin
         }
         HIPCHK(hipGetLastError());
         // the flagged blocks (clustered lambda_min) at the full width; the others exit at once
-        lds_attr_once(attr2r, (const void*)eigmin_lds2<T, true>, (int)LDS_MAX);
-        eigmin_lds2<T, true><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out, redo);
+        lds_attr_once(attr2r, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
+        eigmin_lds2<T><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out, redo);
         HIPCHK(hipGetLastError());
         return;
       }
     }
-    // multi-word: eigmin_lds2 (two barriers per column) unless CLRSDP_EIG_LDS1=1
-    static const bool lds1 = env_on("CLRSDP_EIG_LDS1");
-    if (!std::is_same<T, double>::value && !lds1 && eig2_lds_bytes<T>(nmax) <= LDS_MAX &&
+    // multi-word: eigmin_lds2 (two barriers per column) where its column slots fit
+    if (!std::is_same<T, double>::value && eig2_lds_bytes<T>(nmax) <= LDS_MAX &&
         (sizeof(T) <= 16 || nmax <= 64)) {  // (qd: 8 column slots per lane, n <= 64)
-      static std::atomic<unsigned long long> attr2{0}, attr2f{0};
-      if (newton) {
-        lds_attr_once(attr2, (const void*)eigmin_lds2<T, true>, (int)LDS_MAX);
-        eigmin_lds2<T, true><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out);
-      } else {
-        lds_attr_once(attr2f, (const void*)eigmin_lds2<T, false>, (int)LDS_MAX);
-        eigmin_lds2<T, false><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out);
-      }
+      static std::atomic<unsigned long long> attr2{0};
+      lds_attr_once(attr2, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
+      eigmin_lds2<T><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out);
       HIPCHK(hipGetLastError());
       return;
     }
     if (eig_lds_bytes<T>(nmax) <= LDS_MAX) {
       const size_t lds = eig_lds_bytes<T>(nmax);
-      static std::atomic<unsigned long long> attr_t{0}, attr_f{0};
+      static std::atomic<unsigned long long> attr_t{0};
       lds_attr_once(attr_t, (const void*)eigmin_lds<T, true>, (int)LDS_MAX);
-      lds_attr_once(attr_f, (const void*)eigmin_lds<T, false>, (int)LDS_MAX);
-      if (newton) eigmin_lds<T, true><<<(unsigned)h.size(), 512, lds, s>>>(d, out);
-      else eigmin_lds<T, false><<<(unsigned)h.size(), 512, lds, s>>>(d, out);
+      eigmin_lds<T, true><<<(unsigned)h.size(), 512, lds, s>>>(d, out);
     } else {
       const size_t lds = sizeof(T) * (4 * (size_t)nmax + 256);
       eigmin_batched<T><<<(unsigned)h.size(), 256, lds, s>>>(d, out);
@@ -924,8 +799,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
 // CLRSDP_LU_BLK: unset (-1) the blocked LU chain (getrf_blk_*) where getrf_batched's on-chip
 // panel does not fit; 1 the chain at every size; 0 getrf_batched only (larger matrices: E_ARG)
 inline int lu_blk_mode() {
-  const char* e = std::getenv("CLRSDP_LU_BLK");
-  return !e ? -1 : e[0] != '0' ? 1 : 0;
+  return env_off("CLRSDP_LU_BLK") ? 0 : env_on("CLRSDP_LU_BLK") ? 1 : -1;
 }
 
 // pivoted LU in place (the approx_lu! / approx_inv! fallback): getrf_batched, one workgroup per
@@ -1045,40 +919,23 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
       else if (nmax <= 128) go<128>(s, nb, info);
       else go<256>(s, nb, info);
     } else {
-      using C = RegCfg<T>;
-      static const bool la = !env_off("CLRSDP_CHOL_LA");
-      // blocks n <= 32 on 4 waves -- one per SIMD, the chain alone on its SIMD -- instead of 16
-      // (C5's X/Y blocks <= 18: 980 -> 1007 it/s, round 5; CLRSDP_LA_SMALL=0 keeps 16)
-      static const bool la_small = !env_off("CLRSDP_LA_SMALL");
-      if (la && la_small && nmax <= 32) {
-        if (std::is_same<T, mw::qd>::value && chol_ldl_on())
-          chol_lookahead<T, true, true, 32, 3><<<nb, 256, 0, s>>>(din, dout, dl, info, la_opts());
-        else
-          chol_lookahead<T, true, false, 32, 3><<<nb, 256, 0, s>>>(din, dout, dl, info, la_opts());
-      } else if (la && nmax <= 64) {  // the look-ahead factorisation with L^-1 (SKIP0 as potrf's)
-        if (std::is_same<T, mw::qd>::value && chol_ldl_on())
-          chol_lookahead<T, true, true, 64, 15, true><<<nb, 1024, 0, s>>>(din, dout, dl, info, la_opts());
-        else
-          chol_lookahead<T, true, false, 64, 15, true><<<nb, 1024, 0, s>>>(din, dout, dl, info, la_opts());
-      } else if (chol_packed_on() && nmax <= 64)
-        launch_chol_packed<T, true>(nb, s, din, dout, dl, info);
-      else
-        chol_inv_reg<T, C::TR, C::TC, C::GR, C::GC><<<nb, C::GR * C::GC, 0, s>>>(din, dout, dl, info);
+      // chol_lookahead with L^-1 (quad-double: the square-root-free LDL form).  Blocks n <= 32
+      // on 4 waves -- one per SIMD, the chain alone on its SIMD -- instead of 16 (C5's X/Y
+      // blocks <= 18: 980 -> 1007 it/s, round 5); SKIP0 at 64 as potrf's
+      constexpr bool LDL = std::is_same<T, mw::qd>::value;
+      if (nmax <= 32) chol_lookahead<T, true, LDL, 32, 3><<<nb, 256, 0, s>>>(din, dout, dl, info, la_opts());
+      else if (nmax <= 64) chol_lookahead<T, true, LDL, 64, 15, true><<<nb, 1024, 0, s>>>(din, dout, dl, info, la_opts());
+      else throw ClrsdpError{CLRSDP_E_ARG, "on-chip multi-word factorisation with inverse: n <= 64 only"};
     }
     HIPCHK(hipGetLastError());
   }
   template <int NP>
   void go(hipStream_t s, unsigned nb, int* info) const {
-    // CLRSDP_CHOL_LDS_KB: request at least that much LDS per workgroup, so no 80-KB GEMM
-    // workgroup of a side stream can share the CU with a factorisation (A/B experiment)
-    static const size_t lds = [] {
-      const char* e = std::getenv("CLRSDP_CHOL_LDS_KB");
-      const size_t want = e ? (size_t)std::atoi(e) * 1024 : 0;
-      return std::min<size_t>(std::max(chol_inv_tiles_lds<NP>(), want), 160 * 1024);
-    }();
+    static_assert(sizeof(double) * CholTiles<NP>::END + 16 <= LDS_MAX, "chol_inv_tiles: LDS");
+    const size_t lds = chol_inv_tiles_lds<NP>();
     // raised wave priority: the factorisation's chains keep their issue slots against the side
-    // streams' GEMM waves on the same SIMDs (CLRSDP_CHOL_PRIO=0: default priority)
-    static const int prio = env_off("CLRSDP_CHOL_PRIO") ? 0 : 1;
+    // streams' GEMM waves on the same SIMDs
+    constexpr int prio = 1;
     static std::atomic<unsigned long long> attr{0};
     lds_attr_once(attr, (const void*)chol_inv_tiles<NP>, (int)lds);
     chol_inv_tiles<NP><<<nb, CholTiles<NP>::NTH, lds, s>>>(
@@ -1216,17 +1073,14 @@ struct Solver final : HandleBase {
   // m = L = 1 with rank-1 samples): no scale_cols launch, no scaled copy of V
   bool wa_fused = false;
   GemmPlan<T> p_wA_Ps, p_wA_dXs;
-  // CLRSDP_EXP: development A/B switch for the variant under measurement (0 = the default)
-  const int exp_knob = std::getenv("CLRSDP_EXP") ? std::atoi(std::getenv("CLRSDP_EXP")) : 0;
   bool pending_x21 = false;  // the solves wait for X21 (side stream, iterate)
   hipEvent_t ev_x2 = nullptr, ev_x21 = nullptr;
-  // multi-word S_j / Q <= 64 in the split form (CLRSDP_MW_SPLIT): potrf on the critical path,
+  // multi-word S_j / Q beyond reg_nmax in the split form: potrf on the critical path,
   // L^-1 by four-wave triangular solves of the identity (S_j: on aux2, off the critical path),
   // then the same GEMV solves as the explicit-inverse path
   bool s_split = false, q_split = false, pending_sinv = false;
   bool qf_fresh = false;  // sum_q_slabs wrote Qf = Q for this iteration's factor_q_
-  int64_t s_len = 0;
-  T *SLi = nullptr, *SLid = nullptr, *QLi = nullptr, *QLid = nullptr;  // L^-1 and identity images
+  T *SLi = nullptr, *QLi = nullptr;  // L^-1 of the S_j and of Q
   TrsmPlan<T> t_Sinv, t_Qinv;
   GemmPlan<T> q_t2, q_dx2, q_qinv2;
   hipEvent_t ev_sp = nullptr, ev_sinv = nullptr;
@@ -1406,16 +1260,8 @@ struct Solver final : HandleBase {
     HIPCHK(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
     stream = own_stream;
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    // CLRSDP_ONE_STREAM=1: the side-stream work runs in order on the main stream (experiment:
-    // graph-boundary and join idle time against the lost overlap)
-    if (env_on("CLRSDP_ONE_STREAM")) {
-      aux = aux2 = own_stream;
-    } else {
-      HIPCHK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-      // CLRSDP_FACTOR_SPLIT=0: FACTOR's W1 products stay on the main stream
-      if (env_off("CLRSDP_FACTOR_SPLIT")) aux2 = own_stream;
-      else HIPCHK(hipStreamCreateWithFlags(&aux2, hipStreamNonBlocking));
-    }
+    HIPCHK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&aux2, hipStreamNonBlocking));
     for (hipEvent_t* e : {&ev_m, &ev_x, &ev_s, &ev_r, &ev_qa, &ev_q, &ev_x2, &ev_x21, &ev_ty, &ev_join,
                           &ev_fa, &ev_w, &ev_join2, &ev_sp, &ev_sinv, &ev_dxo, &ev_stx})
       HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -1452,8 +1298,8 @@ struct Solver final : HandleBase {
       if (e) (void)hipEventDestroy(e);
     for (hipGraphExec_t g : gexec)
       if (g) (void)hipGraphExecDestroy(g);
-    if (aux && aux != own_stream) (void)hipStreamDestroy(aux);
-    if (aux2 && aux2 != own_stream) (void)hipStreamDestroy(aux2);
+    if (aux) (void)hipStreamDestroy(aux);
+    if (aux2) (void)hipStreamDestroy(aux2);
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 
@@ -1539,28 +1385,19 @@ struct Solver final : HandleBase {
       reg_blk = nmax_b <= reg_nmax<T>();
       reg_S = nmax_S <= (std::is_same<T, double>::value ? 2 : 1) * reg_nmax<T>();
       reg_Q = n_y <= reg_nmax<T>();
-      // multi-word S_j / Q up to 64: GEMV solves with L^-1 instead of the serial multi-word
-      // vector solves (four 41-us trsv_wave chains per direction at C5).  Default, the split
-      // form: potrf on the critical path and L^-1 = L \ I by four-wave solves (S_j's beside W_j
-      // and the Q chain), C5 891 it/s; CLRSDP_MW_SPLIT=0: the look-ahead factorisation with
-      // L^-1 (90 us longer per factorisation, 827 it/s; CLRSDP_MW_INV_S=0 / _Q=0 then keep
-      // potrf + trsv, 761 it/s).  C4 (dim S_j = 127) unchanged.  Round 5 A/B.
-      if (!std::is_same<T, double>::value && !env_off("CLRSDP_CHOL_LA")) {
-        static const bool split = !env_off("CLRSDP_MW_SPLIT");
-        if (split) {
-          // (double-double S_j up to 128: trsv_wave128 forms L^-1 as it does the vector solves)
-          const int lim = std::is_same<T, mw::dd>::value && !env_off("CLRSDP_TRSV128") ? 128 : 64;
-          s_split = !reg_S && nmax_S <= lim;
-          q_split = !reg_Q && n_y <= 64;
-        } else {
-          if (!env_off("CLRSDP_MW_INV_S")) reg_S = reg_S || nmax_S <= 64;
-          if (!env_off("CLRSDP_MW_INV_Q")) reg_Q = reg_Q || n_y <= 64;
-        }
+      // multi-word S_j / Q beyond the on-chip inverse: GEMV solves with L^-1 instead of the
+      // serial multi-word vector solves (four 41-us trsv_wave chains per direction at C5), in the
+      // split form: potrf on the critical path and L^-1 = L \ I by four-wave solves (S_j's beside
+      // W_j and the Q chain).  Double-double S_j up to 128: trsv_wave128 forms L^-1 as it does
+      // the vector solves.  (DESIGN.md §13 has the round-5 A/B against the other forms.)
+      if (!std::is_same<T, double>::value) {
+        s_split = !reg_S && nmax_S <= (std::is_same<T, mw::dd>::value ? 128 : 64);
+        q_split = !reg_Q && n_y <= 64;
       }
     }
     q_xinv.ta = true;
     q_sx2.tb = q_sy2.tb = true;
-    // L^-1 dM L^-T exactly symmetric: eigmin_reg reads it without a transposed copy
+    // L^-1 dM L^-T exactly symmetric: eigmin_split reads it without a transposed copy
     q_sx2.sym = std::is_same<T, double>::value;
     f_d.ta = true;
     f_x1.tb = true;
@@ -1666,13 +1503,12 @@ struct Solver final : HandleBase {
       // the strip chains need one block size n <= 128 at stride n^2 (one cluster shape: C3 and
       // its shards); by default taken for 64 < n (C2's n = 64 keeps the tiled GEMMs); Z only for
       // m = 1 (no symmetrisation of Z); CLRSDP_CHAIN=0 / 1 forces either
-      const char* ec = std::getenv("CLRSDP_CHAIN");
       bool uni_blk = !lb.empty() && !anyMgt1;
       for (size_t q = 0; q < lb.size() && uni_blk; ++q)
         uni_blk = lb[q].n == lb[0].n && lb[q].off == lb[0].off + (int64_t)q * lb[0].n * lb[0].n;
       const int n0 = lb.empty() ? 0 : lb[0].n;
-      const bool chains = uni_blk && n0 <= 128 && reg_blk && !(ec && ec[0] == '0') &&
-                          ((ec && ec[0] == '1') || n0 > 64);
+      const bool chains = uni_blk && n0 <= 128 && reg_blk && !env_off("CLRSDP_CHAIN") &&
+                          (env_on("CLRSDP_CHAIN") || n0 > 64);
       if (chains) {
         const int nbk = (int)lb.size();
         c_Z.init(n0, nbk, 1, false, false);
@@ -1681,10 +1517,9 @@ struct Solver final : HandleBase {
         c_dY.set(0, dX, Y, R, Xinv, dY);         // dY = X^-1 (R - dX Y)
         // the predictor's dY launch also leaves the partials of <X + dX, Y + dY> (CORRECTOR_R's
         // mu; a flat sum over both triangles, so dY before its symmetrisation gives the same
-        // value); one rank only (CLRSDP_DY_DOT=0: the separate flat_reduce)
-        static const bool dd_env = !env_off("CLRSDP_DY_DOT");
+        // value); one rank only (else the separate flat_reduce)
         dy_dot_cnt = nbk * (int)cdiv(n0, chain::NS);
-        dy_dot_ok = dd_env && world == 1;
+        dy_dot_ok = world == 1;
         if (dy_dot_ok) {
           if (!dotp) dotp = dmalloc<T>(dy_dot_cnt);
           c_dY.u.DA[0] = X; c_dY.u.DdA[0] = dX; c_dY.u.DB[0] = Y;
@@ -1703,16 +1538,15 @@ struct Solver final : HandleBase {
         }
         e_Xs.finalize();
         e_Ys.finalize();
-        // CLRSDP_XY_OVERLAP=1 (round 6): with at most
-        // CLRSDP_XY_OVERLAP_MAX (32) local blocks the X step length (its congruence and eigen
-        // launch) runs on the side stream as soon as the corrector's dX exists, beside dY and
-        // the Y step length.  Measured, not the default.
-        const char* eo = std::getenv("CLRSDP_XY_OVERLAP_MAX");
-        xy_ov_ok = env_on("CLRSDP_XY_OVERLAP") && nb() <= (eo ? std::atoi(eo) : 32);
+        // CLRSDP_XY_OVERLAP=1 (round 6): with at most 32 local blocks the
+        // X step length (its congruence and eigen launch) runs on the side stream as soon as the
+        // corrector's dX exists, beside dY and the Y step length.  Measured, not the default
+        // (DESIGN.md §7).
+        xy_ov_ok = env_on("CLRSDP_XY_OVERLAP") && nb() <= 32;
       }
     }
     n_blk_m = (int)bdm.size();
-    if (std::is_same<T, double>::value && !env_off("CLRSDP_SYM_TILES")) {
+    if (std::is_same<T, double>::value) {
       int nmx = 0;
       for (const LBlk& b : lb) nmx = std::max(nmx, b.n);
       const int nt = (nmx + 31) / 32;
@@ -1792,26 +1626,14 @@ struct Solver final : HandleBase {
       q_dx2.ta = true;
       q_qinv2.ta = true;
       t_W.four = t_Sinv.four = t_Qinv.four = true;
-      auto ident = [&](T*& img, T*& id, const std::vector<std::pair<int64_t, int>>& blocks, int64_t len) {
-        img = dmalloc<T>(len);
-        id = dmalloc<T>(len);
-        std::vector<T> h((size_t)len, T(0.0));
-        for (const auto& b : blocks)
-          for (int i = 0; i < b.second; ++i) h[(size_t)(b.first + (int64_t)i * b.second + i)] = T(1.0);
-        HIPCHK(hipMemcpy(id, h.data(), (size_t)len * sizeof(T), hipMemcpyHostToDevice));
-      };
+      // (the solves take the identity's columns as right-hand sides themselves: vec_rhs())
       if (s_split) {
-        std::vector<std::pair<int64_t, int>> bl;
         int64_t len = 1;
-        for (int c = 0; c < nc(); ++c) {
-          const int D = (int)Ds[oc[c]];
-          bl.push_back({c_Soff[c], D});
-          len = std::max(len, c_Soff[c] + (int64_t)D * D);
-        }
-        ident(SLi, SLid, bl, len);
-        s_len = len;
+        for (int c = 0; c < nc(); ++c)
+          len = std::max(len, c_Soff[c] + (int64_t)Ds[oc[c]] * Ds[oc[c]]);
+        SLi = dmalloc<T>(len);
       }
-      if (q_split) ident(QLi, QLid, {{0, (int)n_y}}, std::max<int64_t>(n_y * n_y, 1));
+      if (q_split) QLi = dmalloc<T>(std::max<int64_t>(n_y * n_y, 1));
     }
     for (int c = 0; c < nc(); ++c) {
       const int j = oc[c];
@@ -1944,12 +1766,6 @@ struct Solver final : HandleBase {
       d_tb = descs.own(tbk);
     }
     if (fast_schur) build_fast_schur();
-    {  // FACTOR's critical-path products run beside the side streams' P, Z and W1 work: raised
-       // wave priority, opt-in with CLRSDP_FACTOR_PRIO=1 (C3 1252-1276 against 1260-1266 it/s,
-       // A/B round 5: the contention is for CUs, not for issue slots)
-      static const bool fp = env_on("CLRSDP_FACTOR_PRIO");
-      f_a.prio = f_b.prio = f_c.prio = f_d.prio = fp;
-    }
     for (GemmPlan<T>* g : {&p_txy, &p_ty, &p_XY, &p_dXdY, &p_xinv, &p_s1x, &p_s1y, &p_s2x, &p_s2y, &p_Q, &p_wA_P,
                            &p_wA_dX, &p_trU_Z, &p_trU_Y, &p_By, &p_Btx, &p_Wt, &p_Wdy, &p_PY,
                            &p_Z, &p_dXY, &p_dY, &q_xinv, &q_sx1, &q_sx2, &q_sy1, &q_sy2, &q_W,
@@ -1961,7 +1777,6 @@ struct Solver final : HandleBase {
     e_XY.finalize();
     for (TrsmPlan<T>* t : {&t_Linv, &t_W, &t_t, &t_Q, &t_sX1, &t_sX2, &t_sY1, &t_sY2, &t_dx, &t_Sinv, &t_Qinv})
       t->finalize();
-    for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q}) f->reg_potrf = true;
     for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q, &e_X, &e_Y}) f->finalize();
   }
 
@@ -2125,8 +1940,7 @@ struct Solver final : HandleBase {
       // shards), and in its ONE form below half the CUs (small cluster counts; at delta <= 64, C2,
       // the D64 instance).  Otherwise the unfused pair, with more and smaller workgroups.
       // CLRSDP_SCHUR_FUSED=0 / 1 forces either.
-      const char* ef = std::getenv("CLRSDP_SCHUR_FUSED");
-      schur_fused = !(ef && ef[0] == '0') && !ptd.empty();
+      schur_fused = !env_off("CLRSDP_SCHUR_FUSED") && !ptd.empty();
       int fwg = 0;
       for (const PairTileDesc& t : ptd) {
         schur_fused = schur_fused && t.del <= 128;
@@ -2144,7 +1958,7 @@ struct Solver final : HandleBase {
       for (const PairTileDesc& t : ptd) fused_d64 = fused_d64 && t.del <= 64;
       for (const PairTileDesc& t : ptd) fused_one = fused_one && (t.del > 64 || fused_d64);
       if (env_on("CLRSDP_SCHUR_FUSED_ONE")) fused_one = true;
-      if (!(ef && ef[0] == '1') && !fused_one) {
+      if (!env_on("CLRSDP_SCHUR_FUSED") && !fused_one) {
         for (const PairTileDesc& t : ptd) schur_fused = schur_fused && t.del > 64;
         schur_fused = schur_fused && fwg >= 128;
       }
@@ -2163,8 +1977,7 @@ struct Solver final : HandleBase {
           fpd.push_back(f);
           fnt.push_back(cdiv(b.K, 64));
         }
-        const char* efy = std::getenv("CLRSDP_SCHUR_FUSED_Y");
-        fused_y = !(efy && efy[0] == '0');
+        fused_y = !env_off("CLRSDP_SCHUR_FUSED_Y");
         fused_one = fused_one && fused_y;  // (instantiated with V^T Y on chip only)
         fused_d64 = fused_d64 && fused_one;   // (instantiated in the ONE form only)
         std::vector<TileRef> ft2d = tile_major(fnt);
@@ -2453,7 +2266,7 @@ struct Solver final : HandleBase {
     if (only_m) {
       if (n_blk_m) blk_sym2<T><<<dim3(n_blk_m, 32), 128, 0, stream>>>(d_blk_m, out, Zm, mode);
     } else if (std::is_same<T, double>::value && mode == 0 && nb() && sym_pairs) {
-      // (fp64: coalesced tile pairs; CLRSDP_SYM_TILES=0 keeps blk_sym2)
+      // (fp64: coalesced tile pairs)
       blk_sym_tiles<<<dim3(nb(), sym_pairs), 256, 0, stream>>>(
           d_blk, reinterpret_cast<double*>(out), reinterpret_cast<const double*>(Zm));
     } else if (nb()) {
@@ -2478,8 +2291,7 @@ struct Solver final : HandleBase {
     p.need_d = need_d;
     p.dim = dimtot;
     p.pd_feas = pd_feas;
-    static const int fold_all = env_off("CLRSDP_FOLD_ALL") ? 0 : 1;
-    p.fold_all = fold_all;
+    p.fold_all = 1;
     return p;
   }
   void set_control(const clrsdp_control* c) override {
@@ -2588,7 +2400,7 @@ struct Solver final : HandleBase {
   // (round 6) a loop body at fp64 forms R = mu_p I - XY in XINV's launch, beside
   // X^-1 = L^-T L^-1: a mixed batch (gemm_f64_dyn, the mu_p diagonal from the scalar slot) instead
   // of a 128^3 GEMM launch of its own on the critical path before chol_inv(X, Y) -- R is first
-  // read by the predictor's Z after SCHUR.  CLRSDP_FUSE_R=0 keeps the separate launch.
+  // read by the predictor's Z after SCHUR.  (The per-stage timing mode keeps the separate launch.)
   bool fuse_r = false;
   GemmPlan<T> p_xir;
   // mu = <X,Y>/dim, mu_p (and the status words cleared, the halt word decided)
@@ -2666,9 +2478,8 @@ struct Solver final : HandleBase {
         }
         // the fused kernel writes the lower triangle of S only when every reader takes that
         // triangle (the fp64 Cholesky FACTOR: chol_inv_tiles, and L21^T = L11^-1 S21^T); the
-        // pivoted LU and the rank-group sums read all of it.  CLRSDP_SCHUR_FULL=1 for A/B
-        static const bool force_full = env_on("CLRSDP_SCHUR_FULL");
-        const bool full = force_full || !fac2 || n_gsum > 0 || lu_sq();
+        // pivoted LU and the rank-group sums read all of it
+        const bool full = !fac2 || n_gsum > 0 || lu_sq();
         s_lower = schur_fused && !full;
         if (schur_fused && fused_d64 && fused_grp2)
           schur_fused_f64<0, true, true, true, true><<<n_fwg, 512, schur_fused::LDS, stream>>>(d_fpd, d_fpt2d, stamps + 4, full);
@@ -2740,7 +2551,7 @@ struct Solver final : HandleBase {
       seg(CLRSDP_INNER_CHOL_S, [&] { ci_S.launch(stream, info + info_S0); });  // S / S11 blocks
       seg(CLRSDP_INNER_CINVB, [&] { f_a.launch(stream, 1.0, 0.0); });          // {L21^T | W}
       // W1 = L11^-1 B1, then W1^T W1 and B2' = B2 - L21 W1: beside the S22 chain in a loop body
-      const bool split = side_x21 && nc2 && aux2 != stream;
+      const bool split = side_x21 && nc2;
       w_split = split;
       auto w_work = [&] {
         seg(CLRSDP_INNER_CINVB, [&] { f_w.launch(stream, 1.0, 0.0); });
@@ -2763,9 +2574,8 @@ struct Solver final : HandleBase {
         if (side_x21) {
           // X21 on the second side stream when W1's products went there (it is idle by now), so
           // that the first side stream is free for the right-hand side and chol(Q) as soon as Q
-          // is summed (CLRSDP_X21_AUX2=0: on the first side stream, behind them)
-          static const bool x21_aux2 = !env_off("CLRSDP_X21_AUX2");
-          const hipStream_t xs = split && x21_aux2 ? aux2 : aux;
+          // is summed
+          const hipStream_t xs = split ? aux2 : aux;
           const hipStream_t main_s = stream;
           HIPCHK(hipEventRecord(ev_x2, main_s));
           HIPCHK(hipStreamWaitEvent(xs, ev_x2, 0));
@@ -2802,8 +2612,6 @@ struct Solver final : HandleBase {
           HIPCHK(hipEventRecord(ev_sp, stream));
           HIPCHK(hipStreamWaitEvent(ls, ev_sp, 0));
         }
-        if (!t_Sinv.vec_rhs())
-          HIPCHK(hipMemcpyAsync(SLi, SLid, (size_t)s_len * sizeof(T), hipMemcpyDeviceToDevice, ls));
         t_Sinv.launch(ls, false);
         if (ls != stream) {
           HIPCHK(hipEventRecord(ev_sinv, ls));
@@ -2824,9 +2632,8 @@ struct Solver final : HandleBase {
   void sum_q_slabs() {
     const int64_t q2 = n_y * n_y;
     // (potrf factors Q in place in Qf: the slab sum writes that copy too, one launch fewer on the
-    // critical path; CLRSDP_Q_DUAL=0 keeps the separate copy)
-    static const bool dual_on = !env_off("CLRSDP_Q_DUAL");
-    T* q_dual = dual_on && !reg_Q && Qf ? Qf : nullptr;
+    // critical path)
+    T* q_dual = !reg_Q && Qf ? Qf : nullptr;
     qf_fresh = q_dual != nullptr;
     if (world == 1 && nc()) {
       slab_sum4<T><<<cdiv(q2, 64), 256, 0, stream>>>(Qslab, nc(), q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
@@ -2856,8 +2663,6 @@ struct Solver final : HandleBase {
       if (!fresh) vlin(Qf, Q, 1.0, nullptr, 0, nullptr, 0, q2);
       f_Q.potrf(stream, info + info_Q0);
       if (q_split) {  // Q^-1 = L_Q^-T L_Q^-1 with L_Q^-1 = L_Q \ I
-        if (!t_Qinv.vec_rhs())
-          HIPCHK(hipMemcpyAsync(QLi, QLid, (size_t)q2 * sizeof(T), hipMemcpyDeviceToDevice, stream));
         t_Qinv.launch(stream, false);
         q_qinv2.launch(stream, 1.0, 0.0);
       }
@@ -2960,7 +2765,7 @@ struct Solver final : HandleBase {
     seg(CLRSDP_INNER_SOLVE, [&] { direction_solves(tag); });
     // dX = P + sum_i dx_i A_i
     seg(CLRSDP_INNER_DX, [&] { weighted_A(dx, p_wA_dX, dX, 1.0); });
-    if (tag == 6 && xy_ov_body && xy_ov_ok && aux != stream) {
+    if (tag == 6 && xy_ov_body && xy_ov_ok) {
       // the X step length beside dY and the Y one (STEP joins it)
       HIPCHK(hipEventRecord(ev_dxo, stream));
       HIPCHK(hipStreamWaitEvent(aux, ev_dxo, 0));
@@ -3030,19 +2835,15 @@ struct Solver final : HandleBase {
     }
     p_Wt.launch(stream, 1.0, 0.0);
     // fp64 with the explicit Q^-1: r = p - sum of the slabs and dy = Q^-1 r in one launch
-    // (slab_qsolve; CLRSDP_SLAB_QSOLVE=0 keeps slab_sum + the GEMV)
+    // (slab_qsolve)
     bool fused_done = false;
     if constexpr (std::is_same<T, double>::value) {
-      static const bool fused_q = [] {
-        const char* e = std::getenv("CLRSDP_SLAB_QSOLVE");
-        return !(e && e[0] == '0');
-      }();
       const size_t lds = ((size_t)n_y + 256) * sizeof(double);
       // every workgroup re-forms all of r: cdiv(n_y, 64) x cnt x n_y slab reads in all.  Fused
-      // only while those stay small (C3: 2 x 64 x 128); otherwise slab_sum forms r once
+      // only while those stay small (C3: 2 x 64 x 128); otherwise slab_sum4 forms r once
       const long long cnt_x = (world == 1 && nc()) ? nc() : world;
       const bool small_sum = (long long)cdiv(n_y, 64) * cnt_x * n_y <= (1LL << 20);
-      if (reg_Q && fused_q && small_sum && lds <= 64 * 1024) {
+      if (reg_Q && small_sum && lds <= 64 * 1024) {
         const double* src = pslab;
         int cnt = nc();
         if (!(world == 1 && nc())) {
@@ -3373,18 +3174,15 @@ struct Solver final : HandleBase {
       StreamSwitch on_aux(stream, aux);
       work();
     };
-    static const bool fr = !env_off("CLRSDP_FUSE_R");
-    fuse_r = fr && std::is_same<T, double>::value && timing != 1 && !p_xir.h.empty();
+    fuse_r = std::is_same<T, double>::value && timing != 1 && !p_xir.h.empty();
     mark(CLRSDP_STAGE_MU_R);
     stage(CLRSDP_STAGE_MU_R, prm, pd_feas);
     // V^T Y of the Schur stage only needs the state: it runs beside chol_inv(X, Y), which leaves
     // half the CUs idle, and SCHUR waits for it (ev_ty) before the pairs launch
-    const bool ty_side = fast_schur && !p_ty.h.empty() && exp_knob != 4 && !(schur_fused && fused_y);
+    const bool ty_side = fast_schur && !p_ty.h.empty() && !(schur_fused && fused_y);
     // P = sum x_i A_i - X - C is first read by the side stream's Z after SCHUR: enqueued there
     // (one fork of the critical path fewer) unless V^T Y needs the fork anyway
-    // (CLRSDP_P_AT_SCHUR=0: beside chol_inv(X, Y) as before)
-    static const bool p_at_schur = !env_off("CLRSDP_P_AT_SCHUR");
-    const bool p_late = p_at_schur && !ty_side;
+    const bool p_late = !ty_side;
     if (!p_late)
       side(ev_m, [&] {
         if (ty_side) {
@@ -3433,16 +3231,14 @@ struct Solver final : HandleBase {
       throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
     mark(CLRSDP_STAGE_RESIDUALS);
     HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
-    static const bool defer_res = !env_off("CLRSDP_DEFER_RES");  // (round 6; =0 for A/B)
-    residuals_finish(defer_res && timing != 1);
+    residuals_finish(timing != 1);
     if (keep_res) copy_guarded(pres, pvec, n_y);
     HIPCHK(hipGetLastError());
     mark(CLRSDP_STAGE_PREDICTOR);
     direction_rest(4);   // Z, U and rhs came from the side stream
-    // (STEP's alpha is formed inside UPDATE's launch; CLRSDP_FUSE_ALPHA=0 keeps the scalar
-    // launch; the per-stage timing mode keeps it so STEP's time includes alpha)
-    static const bool fa = !env_off("CLRSDP_FUSE_ALPHA");
-    fuse_alpha = fa && timing != 1;
+    // (STEP's alpha is formed inside UPDATE's launch; the per-stage timing mode keeps the scalar
+    // launch so STEP's time includes alpha)
+    fuse_alpha = timing != 1;
     xy_ov_body = timing != 1;
     for (int s = CLRSDP_STAGE_CORRECTOR_R; s < CLRSDP_NUM_STAGES; ++s) {
       mark(s);
@@ -3525,9 +3321,9 @@ struct Solver final : HandleBase {
         capturing = false;
         // join the side stream (it may have been forked into the capture) so that the capture
         // ends cleanly and the streams stay usable
-        if (aux != stream && hipEventRecord(ev_join, aux) == hipSuccess)
+        if (hipEventRecord(ev_join, aux) == hipSuccess)
           (void)hipStreamWaitEvent(stream, ev_join, 0);
-        if (aux2 != stream && hipEventRecord(ev_join2, aux2) == hipSuccess)
+        if (hipEventRecord(ev_join2, aux2) == hipSuccess)
           (void)hipStreamWaitEvent(stream, ev_join2, 0);
         (void)hipStreamEndCapture(stream, &graph);
         if (graph) (void)hipGraphDestroy(graph);
@@ -3909,7 +3705,7 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
   CholInvPlan<double> ci;
   GemmPlan<double> g1, g2;
   g2.tb = true;
-  g2.sym = true;  // exactly symmetric L^-1 dM L^-T (eigmin_reg reads only A(i, j))
+  g2.sym = true;  // exactly symmetric L^-1 dM L^-T (eigmin_split reads only A(i, j))
   MatPlan<double> fac, eg;
   TrsmPlan<double> s1, s2;
   std::vector<BlkDesc> big;

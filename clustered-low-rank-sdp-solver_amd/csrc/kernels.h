@@ -5,13 +5,21 @@
 // (j,l) in jl_pairs` loops become the grid.  Layout in HBM: every matrix
 // column-major; block matrices of X, Y, ... concatenated in (j,l) order.
 //
-//   gemm_f64_mfma   C = alpha op(A) op(B) + beta Cin     fp64 matrix cores (v_mfma_f64_16x16x4)
-//   gemm_valu       same for multi-word T                VALU
-//   potrf_batched   in-place lower Cholesky              (spd_inv!/cho!/approx_lu! replacements)
-//   trsm_batched    B <- L^-1 B  or  L^-T B              (approx_solve_tril!/triu!)
-//   eigmin_batched  lambda_min of a symmetric block      (approx_eig_qr! replacement)
-//   schur_assemble  S_j from the pairings BX, BY         (MPMP.jl:1335-1409)
-//   + small elementwise / reduction kernels
+//   gemm_f64_lds / _uni / _dyn, chain_f64
+//                   C = alpha op(A) op(B) + beta Cin     fp64 matrix cores (v_mfma_f64_16x16x4)
+//   gemm_valu_ks    same for multi-word T                VALU
+//   gemv_batched    the N = 1 products
+//   potrf_batched   in-place lower Cholesky              (spd_inv!/cho!/approx_lu! replacements;
+//                   the sizes beyond kernels_dense.h's on-chip factorisations)
+//   trsm_batched, trsv_wave, trsv_wave128
+//                   B <- L^-1 B  or  L^-T B              (approx_solve_tril!/triu!)
+//   getrf_batched, getrf_blk_*
+//                   pivoted LU in place                  (approx_lu! / approx_inv!, the fallback)
+//   eigmin_batched  lambda_min of a symmetric block      (approx_eig_qr!; beyond the LDS kernels)
+//   schur_fused_f64, schur_pairs_f64, schur_gsum, schur_assemble
+//                   S_j from the pairings                (MPMP.jl:1335-1409)
+//   + small elementwise / reduction kernels and the scalar control logic
+// (tools/micro/retired_kernels.h keeps the kernels that only microbenchmarks still launch)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mwfloat.h"
@@ -637,60 +645,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_f64_dyn(const GemmDesc<double>* 
     case 1: gemm_f64_tile<true, false, BK, NW, false>(d, tr.t, smem, al, be, ds, dm); break;
     case 2: gemm_f64_tile<false, true, BK, NW, false>(d, tr.t, smem, al, be, ds, dm); break;
     default: gemm_f64_tile<true, true, BK, NW, false>(d, tr.t, smem, al, be, ds, dm); break;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// GEMM on the VALU for multi-word T: 16x16 tile, 256 threads, one output per thread.
-// ------------------------------------------------------------------------------------------
-template <class T, bool TA, bool TB>
-__global__ __launch_bounds__(256) void gemm_valu(const GemmDesc<T>* __restrict__ descs,
-                                                 const TileRef* __restrict__ t2d, double alpha,
-                                                 double beta) {
-  // 16x16 output tile, one output per thread with two accumulation chains (even / odd k): the
-  // multi-word FMA is a long dependent sequence, so the tile is small enough for a batch of
-  // 64x64 blocks to put two workgroups on every CU (the 32x32 tile with 2x2 outputs per thread
-  // left half the CUs idle at one wave per SIMD)
-  constexpr int BM = 16, BN = 16, BK = 16;
-  __shared__ T As[BK][BM + 1];
-  __shared__ T Bs[BK][BN + 1];
-  const TileRef tr = t2d[blockIdx.x];
-  const GemmDesc<T> d = descs[tr.p];
-  const int t = tr.t;
-  const int m0 = (t / d.tn) * BM, n0 = (t % d.tn) * BN;
-  const int tid = threadIdx.x;
-  const int ti = tid & 15, tj = tid >> 4;
-  T acc0 = T(0.0), acc1 = T(0.0);
-  for (int k0 = 0; k0 < d.K; k0 += BK) {
-    {  // A tile 16 x 16: i contiguous in memory unless TA
-      const int i = TA ? (tid >> 4) : (tid & 15), k = TA ? (tid & 15) : (tid >> 4);
-      const int gi = m0 + i, gk = k0 + k;
-      // (an unconditional load from a clamped index and a component-wise select: a multi-word
-      // value assigned under a branch stayed in scratch memory)
-      const bool in = gi < d.M && gk < d.K;
-      const size_t ia = in ? (TA ? gk + (size_t)gi * d.lda : gi + (size_t)gk * d.lda) : 0;
-      As[k][i] = sel(in, d.A[ia], T(0.0));
-    }
-    {  // B tile 16 x 16: j contiguous in memory iff TB
-      const int j = TB ? (tid & 15) : (tid >> 4), k = TB ? (tid >> 4) : (tid & 15);
-      const int gj = n0 + j, gk = k0 + k;
-      const bool in = gj < d.N && gk < d.K;
-      const size_t ib = in ? (TB ? gj + (size_t)gk * d.ldb : gk + (size_t)gj * d.ldb) : 0;
-      Bs[k][j] = sel(in, d.B[ib], T(0.0));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < BK; k += 2) {
-      acc0 += As[k][ti] * Bs[k][tj];
-      acc1 += As[k + 1][ti] * Bs[k + 1][tj];
-    }
-    __syncthreads();
-  }
-  const int row = m0 + ti, col = n0 + tj;
-  if (row < d.M && col < d.N) {
-    T v = (acc0 + acc1) * T(alpha);
-    if (beta != 0.0) v += d.Cin[row + (size_t)col * d.ldcin] * T(beta);
-    d.C[row + (size_t)col * d.ldc] = v;
   }
 }
 
@@ -1588,10 +1542,10 @@ __device__ __forceinline__ void trsv_fms2(mw::dd& w0, const mw::dd& a0, const mw
 #undef TSB
 }
 template <class T> constexpr size_t trsv_wave_lds() { return sizeof(T) * (64 * 64 + 64); }
-// PF (round 6, late): the staging loads of L are all issued before the pivots' reciprocals and
-// before any of them is used (the loop with a runtime trip count waited on each load in turn:
-// ~n^2 / (128 NW) dependent global-load latencies); the values and their order are unchanged.
-template <class T, bool TRANS, int NW = 4, bool PF = true>
+// (round 6, late) The staging loads of L are all issued before the pivots' reciprocals and
+// before any of them is used (a loop with a runtime trip count waited on each load in turn:
+// ~n^2 / (128 NW) dependent global-load latencies).
+template <class T, bool TRANS, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void trsv_wave(const TrsmDesc<T>* __restrict__ descs,
                                                      const int* __restrict__ t2d) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1601,36 +1555,23 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave(const TrsmDesc<T>* __restri
   const int n = d.n, tid = threadIdx.x, lane = tid & 63;
   const T* L = d.L;
   const size_t ldl = d.ldl;
-  constexpr int NT = 64 * NW, IT = PF ? (64 * 64 + NT - 1) / NT : 1;
+  constexpr int NT = 64 * NW, IT = (64 * 64 + NT - 1) / NT;
   T lv[IT];
-  if constexpr (PF) {
 #pragma unroll
-    for (int u = 0; u < IT; ++u) {
-      const int e = tid + NT * u, i = e % n, j = e / n;
-      lv[u] = (e < n * n && i > j) ? L[i + (size_t)j * ldl] : T(0.0);
-    }
+  for (int u = 0; u < IT; ++u) {
+    const int e = tid + NT * u, i = e % n, j = e / n;
+    lv[u] = (e < n * n && i > j) ? L[i + (size_t)j * ldl] : T(0.0);
   }
   if (tid < n) rdg[tid] = recip_fast(L[tid + (size_t)tid * ldl]);
   __syncthreads();
   // column q of L (rows > q) scaled by 1/l_qq; transposed: row q (columns < q), read as column
-  if constexpr (PF) {
 #pragma unroll
-    for (int u = 0; u < IT; ++u) {
-      const int e = tid + NT * u, i = e % n, j = e / n;
-      if (e < n * n && i > j) {
-        const T v = lv[u] * rdg[TRANS ? i : j];
-        if (TRANS) Ls[j + 64 * i] = v;
-        else Ls[i + 64 * j] = v;
-      }
-    }
-  } else {
-    for (int e = tid; e < n * n; e += 64 * NW) {
-      const int i = e % n, j = e / n;  // coalesced: i runs over the rows of L
-      if (i > j) {
-        const T v = L[i + (size_t)j * ldl] * rdg[TRANS ? i : j];
-        if (TRANS) Ls[j + 64 * i] = v;
-        else Ls[i + 64 * j] = v;
-      }
+  for (int u = 0; u < IT; ++u) {
+    const int e = tid + NT * u, i = e % n, j = e / n;  // coalesced: i runs over the rows of L
+    if (e < n * n && i > j) {
+      const T v = lv[u] * rdg[TRANS ? i : j];
+      if (TRANS) Ls[j + 64 * i] = v;
+      else Ls[i + 64 * j] = v;
     }
   }
   __syncthreads();
@@ -1639,40 +1580,28 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave(const TrsmDesc<T>* __restri
   T* B = d.B + (size_t)c * d.ldb;
   T v = T(0.0);
   if (lane < n) v = trsv_rhs(d, B, lane, c);
-  if constexpr (PF) {
-    // branch-free steps with the next step's coefficient read ahead of this step's arithmetic
-    // (the exec-masked form waited on each LDS read); inactive lanes keep v by a select, so
-    // every active lane runs the same operations in the same order
-    if (!TRANS) {
-      T c = Ls[lane];
-      for (int q = 0; q + 1 < n; ++q) {
-        T nx = c;
-        if (q + 2 < n) nx = Ls[lane + 64 * (q + 1)];
-        const T vq = readlane_t(v, q);
-        const T w = trsv_fms(v, c, vq);
-        v = sel(lane > q && lane < n, w, v);
-        c = nx;
-      }
-    } else {
-      T c = Ls[lane + 64 * (n - 1)];
-      for (int q = n - 1; q > 0; --q) {
-        T nx = c;
-        if (q > 1) nx = Ls[lane + 64 * (q - 1)];
-        const T vq = readlane_t(v, q);
-        const T w = trsv_fms(v, c, vq);
-        v = sel(lane < q, w, v);
-        c = nx;
-      }
-    }
-  } else if (!TRANS) {
+  // branch-free steps with the next step's coefficient read ahead of this step's arithmetic
+  // (an exec-masked form waited on each LDS read); inactive lanes keep v by a select, so
+  // every active lane runs the same operations in the same order
+  if (!TRANS) {
+    T c = Ls[lane];
     for (int q = 0; q + 1 < n; ++q) {
+      T nx = c;
+      if (q + 2 < n) nx = Ls[lane + 64 * (q + 1)];
       const T vq = readlane_t(v, q);
-      if (lane > q && lane < n) v = v - Ls[lane + 64 * q] * vq;
+      const T w = trsv_fms(v, c, vq);
+      v = sel(lane > q && lane < n, w, v);
+      c = nx;
     }
   } else {
+    T c = Ls[lane + 64 * (n - 1)];
     for (int q = n - 1; q > 0; --q) {
+      T nx = c;
+      if (q > 1) nx = Ls[lane + 64 * (q - 1)];
       const T vq = readlane_t(v, q);
-      if (lane < q) v = v - Ls[lane + 64 * q] * vq;
+      const T w = trsv_fms(v, c, vq);
+      v = sel(lane < q, w, v);
+      c = nx;
     }
   }
   if (lane < n) B[lane] = v * rdg[lane];
@@ -1682,10 +1611,9 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave(const TrsmDesc<T>* __restri
 // rows r and r + 64, and the scaled L passes through LDS in chunks of 32 steps (the whole matrix
 // would not fit), staged by the workgroup between two barriers per chunk.
 template <class T> constexpr size_t trsv_wave128_lds() { return sizeof(T) * (32 * 128 + 128); }
-// PF (round 6, late): the next chunk's loads are issued into registers before the current
-// chunk's steps, so they arrive under its chain (the staging loop waited on each load in turn);
-// the values and their order are unchanged.
-template <class T, bool TRANS, int NW = 4, bool PF = true>
+// (round 6, late) The next chunk's loads are issued into registers before the current chunk's
+// steps, so they arrive under its chain (a staging loop waits on each load in turn).
+template <class T, bool TRANS, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void trsv_wave128(const TrsmDesc<T>* __restrict__ descs,
                                                         const int* __restrict__ t2d) {
   constexpr int CH = 32;
@@ -1706,7 +1634,7 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave128(const TrsmDesc<T>* __res
   const int nch = (n + CH - 1) / CH;
   // (the register image of a chunk only where it fits beside the step loop's operands: not for
   // quad-double at 1024 threads, 128 VGPRs)
-  constexpr bool SPF = PF && (sizeof(T) <= 16 || NW <= 4);
+  constexpr bool SPF = sizeof(T) <= 16 || NW <= 4;
   constexpr int NT = 64 * NW, IT = SPF ? (CH * 128 + NT - 1) / NT : 1;
   T lv[IT];
   auto loadc = [&](int ci) {  // chunk ci's entries of L into registers
@@ -1748,7 +1676,7 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave128(const TrsmDesc<T>* __res
     if constexpr (SPF) {
       if (ci + 1 < nch) loadc(ci + 1);  // in flight under this chunk's chain
     }
-    if (act && PF) {
+    if (act) {
       // both rows of the lane every step, branch-free (their two chains interleave), with the
       // next step's coefficients read ahead; inactive rows keep their value by a select
       int qq = TRANS ? qn - 1 : 0;
@@ -1768,13 +1696,6 @@ __global__ __launch_bounds__(64 * NW) void trsv_wave128(const TrsmDesc<T>* __res
         c0 = n0;
         c1 = n1;
         qq = qn1;
-      }
-    } else if (act) {
-      for (int u = 0; u < qn; ++u) {
-        const int qq = TRANS ? qn - 1 - u : u, q = q0 + qq;
-        const T vq = readlane_t(sel(q < 64, v0, v1), q & 63);
-        if (TRANS ? lane < q : (lane > q && lane < n)) v0 = v0 - Ls[lane + 128 * qq] * vq;
-        if (TRANS ? lane + 64 < q : (lane + 64 > q && lane + 64 < n)) v1 = v1 - Ls[lane + 64 + 128 * qq] * vq;
       }
     }
   }
@@ -2936,34 +2857,6 @@ struct BlkDesc {
   int pad;
 };
 
-// out = a*X + b*Y (+ s*I with s = *sc if sc != nullptr)
-template <class T>
-__global__ void blk_axpby(const BlkDesc* __restrict__ bd, T* out, const T* X, const T* Y, double a,
-                          double b, const T* sc, double sc_mult) {
-  const BlkDesc B = bd[blockIdx.x];
-  const int nn = B.n * B.n;
-  T s = T(0.0);
-  if (sc) s = (*sc) * T(sc_mult);
-  for (int e = threadIdx.x; e < nn; e += blockDim.x) {
-    T v = T(0.0);
-    if (a != 0.0) v += X[B.off + e] * T(a);
-    if (b != 0.0) v += Y[B.off + e] * T(b);
-    if (sc && (e % B.n) == (e / B.n)) v += s;
-    out[B.off + e] = v;
-  }
-}
-
-// *flag = OR of info[0..n): a failed factorisation anywhere in this iteration
-__global__ void status_reduce(const int* info, int n, int* flag) {
-  __shared__ int any;
-  if (threadIdx.x == 0) any = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += blockDim.x)
-    if (info[i]) atomicOr(&any, 1);
-  __syncthreads();
-  if (threadIdx.x == 0) *flag = any;
-}
-
 // R_b += s I with s = (*sc) * mult; one workgroup per block
 template <class T>
 __global__ void diag_add(const BlkDesc* __restrict__ bd, T* R, const T* sc, double mult) {
@@ -3040,17 +2933,6 @@ __global__ __launch_bounds__(256) void blk_sym_tiles(const BlkDesc* __restrict__
   }
 }
 
-// X += alpha * dX with alpha = *sc  (skipped when *flag != 0: the state survives a failed step)
-template <class T>
-__global__ void blk_axpy_dev(const BlkDesc* __restrict__ bd, T* X, const T* dX, const T* sc,
-                             const int* flag) {
-  if (*flag) return;
-  const BlkDesc B = bd[blockIdx.x];
-  const int nn = B.n * B.n;
-  const T a = *sc;
-  for (int e = threadIdx.x; e < nn; e += blockDim.x) X[B.off + e] = X[B.off + e] + a * dX[B.off + e];
-}
-
 // identity
 template <class T>
 __global__ void blk_identity(const BlkDesc* __restrict__ bd, T* out) {
@@ -3058,58 +2940,6 @@ __global__ void blk_identity(const BlkDesc* __restrict__ bd, T* out) {
   const int nn = B.n * B.n;
   for (int e = threadIdx.x; e < nn; e += blockDim.x)
     out[B.off + e] = T(((e % B.n) == (e / B.n)) ? 1.0 : 0.0);
-}
-
-// out = (Z + Z^T)/2   (mode 0);  out = upper triangle mirrored (mode 1, Symmetric(.)) ;
-// out = Z^T (mode 2)
-template <class T>
-__global__ void blk_sym(const BlkDesc* __restrict__ bd, T* out, const T* Z, int mode) {
-  const BlkDesc B = bd[blockIdx.x];
-  const int n = B.n;
-  const T* z = Z + B.off;
-  T* o = out + B.off;
-  if (mode == 2) {
-    for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-      const int i = e % n, j = e / n;
-      o[i + (size_t)j * n] = z[j + (size_t)i * n];
-    }
-    return;
-  }
-  // in-place safe: each unordered pair handled by one thread
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e % n, j = e / n;
-    if (i > j) {
-      T v;
-      if (mode == 0) v = (z[i + (size_t)j * n] + z[j + (size_t)i * n]) * T(0.5);
-      else v = z[j + (size_t)i * n];
-      o[i + (size_t)j * n] = v;
-      o[j + (size_t)i * n] = v;
-    } else if (i == j) {
-      o[i + (size_t)j * n] = z[i + (size_t)j * n];
-    }
-  }
-}
-
-// per-block reductions: op 0 = sum X.*Y, op 1 = sum (X+dX).*(Y+dY), op 2 = max |X|
-template <class T>
-__global__ __launch_bounds__(256) void blk_reduce(const BlkDesc* __restrict__ bd, const T* X,
-                                                  const T* Y, const T* dX, const T* dY, int op,
-                                                  T* __restrict__ partial) {
-  __shared__ T red[256];
-  const BlkDesc B = bd[blockIdx.x];
-  const int nn = B.n * B.n;
-  T acc = T(0.0);
-  for (int e = threadIdx.x; e < nn; e += blockDim.x) {
-    const size_t o = B.off + e;
-    if (op == 0) acc += X[o] * Y[o];
-    else if (op == 1) acc += (X[o] + dX[o]) * (Y[o] + dY[o]);
-    else {
-      const T a = Num<T>::abs_(X[o]);
-      if (a > acc) acc = a;
-    }
-  }
-  T r = (op == 2) ? block_max(acc, red) : block_sum(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 
 // vector reductions over [0, n): op 0 = sum a.*b, op 2 = max |a|; single workgroup of
@@ -3203,28 +3033,8 @@ __global__ void ordered_reduce(const T* in, int cnt, long long stride, int op, T
   *out = acc;
 }
 
-// out[e] = sum_{i<cnt} in[i*stride + e]  (fixed order), e < n
-// (optionally out[e] = cbase*base[e] + csum*sum, the two vector updates that follow a slab sum)
-template <class T>
-__global__ void slab_sum(const T* in, int cnt, long long stride, long long n, T* out,
-                         const T* base = nullptr, double cbase = 0.0, double csum = 1.0) {
-  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  T acc = in[e];
-  int i = 1;
-  for (; i + 7 < cnt; i += 8) {  // 8 loads in flight, summed in slab order
-    T v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = in[(size_t)(i + u) * stride + e];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc += v[u];
-  }
-  for (; i < cnt; ++i) acc += in[(size_t)i * stride + e];
-  if (base) acc = base[e] * T(cbase) + acc * T(csum);
-  out[e] = acc;
-}
-
-// slab_sum with the slabs split into 4 contiguous chunks (fixed order inside each, then
+// out[e] = sum_{i<cnt} in[i*stride + e], e < n (optionally cbase*base[e] + csum*sum), in a fixed
+// order: the slabs split into 4 contiguous chunks (fixed order inside each, then
 // ((c0 + c1) + (c2 + c3))): 256 threads = 64 elements x 4 chunks, each chunk's loads 8 in flight,
 // so a sum over 64 slabs takes two memory latencies instead of eight.  grid = cdiv(n, 64).
 template <class T>
@@ -3258,7 +3068,7 @@ __global__ __launch_bounds__(256) void slab_sum4(const T* in, int cnt, long long
   if (out2) out2[e] = acc;
 }
 
-// dy = Q^-1 r with r = cbase*base + csum*sum_{i<cnt} in[i*stride + .] (slab_sum's order): the
+// dy = Q^-1 r with r = cbase*base + csum*sum_{i<cnt} in[i*stride + .] (slab_sum4's order): the
 // slab sum and the Q^-1 GEMV of the block solve (MPMP.jl:1758-1764) in one launch.  Every
 // workgroup forms all of r in LDS (n values, a few KB), then 64 rows of the product: 4 column
 // chunks per row (coalesced reads of the column-major Q^-1), summed in a fixed order.
@@ -3316,19 +3126,6 @@ __global__ void vec_lin(T* out, const T* x, double a, const T* y, double b, cons
   }
 }
 
-// fill rectangles (rows x cols, column-major with ld) with v; blockIdx.y = rectangle
-struct RectDesc {
-  void* p;
-  int rows, cols, ld;
-};
-template <class T>
-__global__ void rect_fill(const RectDesc* __restrict__ rd, double v) {
-  const RectDesc R = rd[blockIdx.y];
-  T* p = reinterpret_cast<T*>(R.p);
-  for (int c = blockIdx.x; c < R.cols; c += gridDim.x)
-    for (int r = threadIdx.x; r < R.rows; r += blockDim.x) p[r + (size_t)c * R.ld] = T(v);
-}
-
 // out[0..n) = v
 // dst = src unless *halt (the loop body was skipped by device-side termination): keeps P, p, d
 // of the last loop body that ran for the pipelined loop
@@ -3367,40 +3164,6 @@ template <class T>
 __global__ void vec_fill(T* out, double v, long long n) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) out[e] = T(v);
-}
-
-// x += (*sc) * dx
-// x_q += alpha_q dx_q for up to 4 vectors (blockIdx.y = q), unless *flag (failed factorisation)
-template <class T> struct AxpyItem {
-  T* x;
-  const T* dx;
-  const T* alpha;
-  long long n;
-};
-template <class T> struct AxpyList { AxpyItem<T> it[4]; };
-// guard: skip when any status word info[0..ninfo) is set (a factorisation failed)
-template <class T>
-__global__ void vec_axpy_list(AxpyList<T> L, const int* info, int ninfo) {
-  __shared__ int any;
-  if (threadIdx.x == 0) any = 0;
-  __syncthreads();
-  for (int i = threadIdx.x; i < ninfo; i += blockDim.x)
-    if (info[i]) any = 1;
-  __syncthreads();
-  if (any) return;
-  const AxpyItem<T> I = L.it[blockIdx.y];
-  const T a = *I.alpha;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < I.n;
-       e += (long long)gridDim.x * blockDim.x)
-    I.x[e] = I.x[e] + a * I.dx[e];
-}
-template <class T>
-__global__ void vec_axpy_dev(T* x, const T* dx, const T* sc, long long n, const int* flag) {
-  if (*flag) return;
-  const T a = *sc;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n;
-       e += (long long)gridDim.x * blockDim.x)
-    x[e] = x[e] + a * dx[e];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3594,7 +3357,7 @@ template <class T> struct ScalarParams {
   int need_p, need_d;
   int nred;
   int zero_cy;  // which == 3 without C: <C,Y> = 0
-  int fold_all;  // fp64: fold_all_f64 (all loads of all folds in flight; CLRSDP_FOLD_ALL=0: off)
+  int fold_all;  // fp64: fold_all_f64 (all loads of all folds in flight); the host always sets 1
   int zero_n;   // zero the status words zero_ptr[0..zero_n) (start of an iteration)
   int* zero_ptr;
   int* halt_ptr;  // which == 0: status word "skip this loop body" (device-decided termination)
@@ -3833,66 +3596,6 @@ __global__ __launch_bounds__(64) void scalar_kernel(T* scg, ScalarParams<T> p, i
     for (int e = lane; e < p.nguard; e += 64) fl = fl || p.guard[e] != 0;
   const bool failed = __any(fl);
   if (lane == 0) scalar_logic(sc, p, which, failed);
-}
-
-// x += alpha_p dx, y += alpha_d dy (guarded), then <c,x>, <b,y> and the objectives
-// (MPMP.jl:877-878, 940-941; one rank, C = 0).  One 1024-thread workgroup.
-template <class T>
-__global__ __launch_bounds__(1024) void update_small(T* __restrict__ x, const T* __restrict__ dx,
-                                                     long long nx, T* __restrict__ y,
-                                                     const T* __restrict__ dy, long long ny,
-                                                     const T* __restrict__ c,
-                                                     const T* __restrict__ b, T* sc,
-                                                     const int* info, int ninfo,
-                                                     ScalarParams<T> p) {
-  const T b0 = p.b0;
-  __shared__ T red[1024];
-  __shared__ int any;
-  const int tid = threadIdx.x;
-  if (tid == 0) any = 0;
-  __syncthreads();
-  for (int i = tid; i < ninfo; i += 1024)
-    if (info[i]) any = 1;
-  __syncthreads();
-  const bool upd = !any;
-  const T ap = sc[SC_ALPHA_P], ad = sc[SC_ALPHA_D];
-  T acc = T(0.0);
-  // (restrict + unroll: the loads of several elements are in flight together; the per-thread
-  // accumulation order is unchanged)
-#pragma unroll 8
-  for (long long e = tid; e < nx; e += 1024) {
-    T v = x[e];
-    if (upd) { v = v + ap * dx[e]; x[e] = v; }
-    acc += c[e] * v;
-  }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s2 = 512; s2 > 0; s2 >>= 1) {
-    if (tid < s2) red[tid] = red[tid] + red[tid + s2];
-    __syncthreads();
-  }
-  const T cx = red[0];
-  __syncthreads();
-  acc = T(0.0);
-  for (long long e = tid; e < ny; e += 1024) {
-    T v = y[e];
-    if (upd) { v = v + ad * dy[e]; y[e] = v; }
-    acc += b[e] * v;
-  }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s2 = 512; s2 > 0; s2 >>= 1) {
-    if (tid < s2) red[tid] = red[tid] + red[tid + s2];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    sc[SC_DOT_CX] = cx;
-    sc[SC_DOT_CY] = T(0.0);
-    sc[SC_DOT_BY] = red[0];
-    sc[SC_POBJ] = cx + b0;
-    sc[SC_DOBJ] = red[0] + b0;
-    control_update(sc, p, false);
-  }
 }
 
 }  // namespace clrsdp

@@ -13,7 +13,7 @@ import _clrsdp_pkg
 # known spills, off every benchmarked configuration (C1-C5):
 ALLOWED = (
     "getrf_batched<",   # the pivoted-LU fallback (approx_lu!), taken only when Cholesky fails
-    "potrf_batched<",   # the panel potrf kept for CLRSDP_CHOL_LA=0 / CLRSDP_REG_POTRF=0
+    "potrf_batched<",   # the panel potrf beyond chol_lookahead's sizes (dd > 128 with CLRSDP_POTRF_BLK=0, qd > 64)
     # quad-double X / Y blocks of 33..64 with L^-1 at 1024 threads (128 VGPRs per lane); C5's
     # X / Y blocks are <= 18 and take the 256-thread instance, which does not spill
     "chol_lookahead<mw::qd, true,",

@@ -379,8 +379,9 @@ def test_stage_parity_sphere_packing_shape_qd(pk, oracle):
 def test_stage_parity_dd_c4_shape(pk, bits, variant, monkeypatch):
     """Config 4 at its own cluster shape (J = 2, delta = 64, rank 2, n_y = 64, dim_S = 127,
     blocks of 64) at double-double against the 128- and 256-bit oracle: drives
-    potrf_batched<dd> / trsm_batched<dd> (dim_S > 64), chol_inv_reg<dd> and eigmin_lds<dd> at
-    n = 64 (MPMP.jl:1433-1465, 762-801, 1829-1898).  dd carries ~106 bits; 1e-25 relative
+    potrf_blk_* / trsv_wave128<dd> (dim_S > 64, the split form), chol_lookahead<dd> with L^-1
+    and eigmin_mx<dd> (eigmin_lds2<dd> behind it) at n = 64 (MPMP.jl:1433-1465, 762-801,
+    1829-1898).  dd carries ~106 bits; 1e-25 relative
     (scale-aware) leaves ~6 orders for the conditioning of S_j at this state.  Both forms of the
     Schur pairings: only the upper tiles of V^T X^-1 V, V^T Y V with schur_assemble reading
     (min, max) (the m = 1 default, round 6) and the full products (CLRSDP_MW_PAIR_UPPER=0); both
@@ -420,8 +421,9 @@ def test_stage_parity_dd_late_iterate(pk, variant, monkeypatch):
 
 
 def test_stage_parity_qd_twin(pk):
-    """Quad-double twin (J = 2, delta = 32, rank 2, n_y = 32, dim_S = 63): chol_inv_reg<qd> at
-    n = 32, potrf_batched<qd> / trsm_batched<qd> at dim_S > 32, eigmin_lds<qd> at n = 32,
+    """Quad-double twin (J = 2, delta = 32, rank 2, n_y = 32, dim_S = 63): the 4-wave
+    chol_lookahead<qd> (LDL, with L^-1) at n = 32, the 16-wave one as potrf with trsv_wave<qd>
+    (the split form) at dim_S > 32, eigmin_mx<qd> (eigmin_lds2<qd> behind it) at n = 32,
     against the 256-bit oracle at 1e-50 relative (qd carries ~212 bits)."""
     _stage_compare_fixture(pk, "qd32", 4, 1e-50, 256)
 

@@ -3,7 +3,7 @@
 # regression hunt / quick sweep): prints the setting, exit code and iterations/s.  A run that
 # ends with a library error (exit 1) does not stop the sweep; any other failure (a time limit,
 # an abort, a fault) ends it at once.
-#   bash tools/env_sweep.sh "--clusters 8 --steps 300" NONE CLRSDP_DY_DOT=0 CLRSDP_CHAIN=0 ...
+#   bash tools/env_sweep.sh "--clusters 8 --steps 300" NONE CLRSDP_SCHUR_FUSED=0 CLRSDP_CHAIN=0 ...
 set -uo pipefail
 ARGS=$1; shift
 export TMPDIR=/tmp

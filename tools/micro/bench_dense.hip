@@ -6,6 +6,7 @@
 #include <vector>
 #include <cmath>
 #include "../../clustered-low-rank-sdp-solver_amd/csrc/kernels_dense.h"
+#include "retired_kernels.h"
 using namespace clrsdp;
 #define CK(x) do{hipError_t e=(x); if(e!=hipSuccess){printf("HIP %s @%d\n",hipGetErrorString(e),__LINE__); exit(1);} }while(0)
 

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../../clustered-low-rank-sdp-solver_amd/csrc/kernels_dense.h"
+#include "retired_kernels.h"
 using namespace clrsdp;
 using mw::dd;
 using mw::qd;

@@ -56,11 +56,11 @@ void run(const char* name, int n, int nb) {
   const size_t l1 = sizeof(T) * ((size_t)n * n + (n <= 64 ? 14 : 10) * n + 40);
   const size_t l2 = eig2_lds_bytes<T>(n);
   CK(hipFuncSetAttribute((const void*)eigmin_lds<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   const float t1 = timeit([&] { eigmin_lds<T, true><<<nb, 512, l1>>>(dd_, dE); });
-  const float t2 = timeit([&] { eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE + nb); });
-  const float t3 = timeit([&] { eigmin_lds2<T, true, 1><<<nb, 512, l2>>>(dd_, dE + 2 * nb); });
+  const float t2 = timeit([&] { eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE + nb); });
+  const float t3 = timeit([&] { eigmin_lds2<T, 1><<<nb, 512, l2>>>(dd_, dE + 2 * nb); });
   std::vector<T> ev(2 * nb);
   CK(hipMemcpy(ev.data(), dE, 2 * nb * sizeof(T), hipMemcpyDeviceToHost));
   double md = 0.0;

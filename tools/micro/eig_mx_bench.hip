@@ -104,23 +104,23 @@ void run(const char* name, int n, int nb, int family, int gexp) {
   CK(hipMalloc(&dd_, nb * sizeof(MatDesc<T>)));
   CK(hipMemcpy(dd_, din.data(), nb * sizeof(MatDesc<T>), hipMemcpyHostToDevice));
   const size_t l2 = eig2_lds_bytes<T>(n), lm = eigmx_lds_bytes<T>(n);
-  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  CK(hipFuncSetAttribute((const void*)eigmin_lds2<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   CK(hipFuncSetAttribute((const void*)eigmin_mx<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - EIGMX_STATIC_LDS));
-  const float t2 = timeit([&] { eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE); });
+  const float t2 = timeit([&] { eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE); });
   unsigned zero = 0, fb = 0;
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_eigmx_fallbacks), &zero, sizeof(zero)));
   eigmin_mx<T><<<nb, 576, lm>>>(dd_, dE + nb, redo);
-  eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
+  eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
   CK(hipDeviceSynchronize());
   CK(hipMemcpyFromSymbol(&fb, HIP_SYMBOL(g_eigmx_fallbacks), sizeof(fb)));
   const float tm = timeit([&] {
     eigmin_mx<T><<<nb, 576, lm>>>(dd_, dE + nb, redo);
-    eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
+    eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
   });
   CK(hipFuncSetAttribute((const void*)eigmin_mx<T, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   const float tl = timeit([&] {
     eigmin_mx<T, 0, 0><<<nb, 512, lm>>>(dd_, dE + nb, redo);
-    eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
+    eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
   });
   // diagnostics of the DBG instance: phase stamps (s_memtime ticks) averaged over the
   // blocks, and eta / lambda / lambda_2 / rho / Temple width of the first rejected blocks
@@ -128,7 +128,7 @@ void run(const char* name, int n, int nb, int family, int gexp) {
   std::vector<double> dz(256 * 24, 0.0);
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_eigmx_dbg), dz.data(), dz.size() * sizeof(double)));
   eigmin_mx<T, 1><<<nb, 576, lm>>>(dd_, dE + nb, redo);
-  eigmin_lds2<T, true, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
+  eigmin_lds2<T, 0><<<nb, 512, l2>>>(dd_, dE + nb, redo);
   CK(hipDeviceSynchronize());
   CK(hipMemcpyFromSymbol(dz.data(), HIP_SYMBOL(g_eigmx_dbg), dz.size() * sizeof(double)));
   {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../../clustered-low-rank-sdp-solver_amd/csrc/kernels_dense.h"
+#include "retired_kernels.h"
 using namespace clrsdp;
 #define CK(x) do{hipError_t e=(x); if(e!=hipSuccess){printf("HIP %s @%d\n",hipGetErrorString(e),__LINE__); return 1;} }while(0)
 

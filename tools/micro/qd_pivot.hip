@@ -60,7 +60,7 @@ int main() {
   double m1 = 0, m2 = 0;
   for (int i = 0; i < n; ++i) { m1 = fmax(m1, e[2 * i]); m2 = fmax(m2, e[2 * i + 1]); }
   const int reps = 64;
-  chain<<<1, 1>>>(dd_, dout, clk, reps);
+  ::chain<<<1, 1>>>(dd_, dout, clk, reps);
   long long c;
   CK(hipMemcpy(&c, clk, sizeof(c), hipMemcpyDeviceToHost));
   printf("pivot_sqrt<qd>%s: max |s^2-d|/d %.2e, max |s r - 1| %.2e, %.0f cycles per dependent pivot\n",

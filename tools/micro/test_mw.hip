@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <vector>
 #include "../../clustered-low-rank-sdp-solver_amd/csrc/kernels.h"
+#include "retired_kernels.h"
 using namespace clrsdp;
 using mw::dd;
 using mw::qd;

@@ -33,7 +33,6 @@ FAMILIES = {
     "chain_f64 (U = Z V + rhs)": ("chain_f64<false, false, true>",),
     "chol_inv_tiles<128>": ("chol_inv_tiles<128>",),
     "eigmin_split": ("eigmin_split",),
-    "eigmin_reg": ("eigmin_reg",),
     "schur_fused_f64": ("schur_fused_f64",),
 }
 
