@@ -1962,6 +1962,16 @@ struct Solver final : HandleBase {
         for (const PairTileDesc& t : ptd) schur_fused = schur_fused && t.del > 64;
         schur_fused = schur_fused && fwg >= 128;
       }
+      // The fused kernel's rank-2 group-sum epilogue is a template parameter of the whole launch
+      // (GRP2: every descriptor grp = 2), not a branch on d.grp.  A handle that mixes all-rank-2
+      // clusters with others (grp = 1: S written per entry, or G for schur_gsum) would have the
+      // group sums applied to those too, so it takes the unfused pair, whose schur_pairs_f64
+      // branches per descriptor -- also under CLRSDP_SCHUR_FUSED=1.
+      {
+        bool all_grp2 = true;
+        for (const PairTileDesc& t : ptd) all_grp2 = all_grp2 && t.grp == 2;
+        if (any_grp2 && !all_grp2) schur_fused = false;
+      }
       if (schur_fused) {
         std::vector<FusedPairDesc> fpd;
         std::vector<int> fnt;

@@ -20,10 +20,20 @@ def main():
     world = int(os.environ["WORLD_SIZE"])
     backend = sys.argv[4] if len(sys.argv) > 4 else "gloo"
     ex = cdist.RcclExchange(0) if backend == "rccl" else cdist.TorchExchange(0, backend="gloo")
-    J = int(os.environ.get("CLRSDP_TEST_J", "5"))
-    cons, b = pk.synth(seed=12, J=J, delta=16, rank=1, n_y=9, m=1)
+    J = os.environ.get("CLRSDP_TEST_J", "5")
+    if J == "mixed":  # the M-T instance of tests/helpers.py (direct, grp2, gsum and L = 2 clusters)
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import helpers
+        cons, b = helpers.mixed_instance(pk, "M-T")
+    else:
+        cons, b = pk.synth(seed=12, J=int(J), delta=16, rank=1, n_y=9, m=1)
     bi = pk.get_block_info(cons)
     owned = pk.partition_clusters(bi, world)[rank]
+    if J == "mixed":
+        # the balancer's split of M-T is the contiguous {0, 1} | {2, 3}: interleave instead, so
+        # that each shard skips a cluster and only rank 1 holds the all-rank-2 (grp2) one
+        assert world == 2
+        owned = [[0, 2], [1, 3]][rank]
     dev = pk.DeviceSolver(cons, b, bi, device=0, rank=rank, world=world, owned=owned)
     ex.attach(dev)
     if len(sys.argv) > 3 and sys.argv[3] == "solve":

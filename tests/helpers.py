@@ -142,6 +142,138 @@ def residual_scales(cons, b, X):
             "d": float(max(np.max(np.abs(np.array(c.c, dtype=float))) for c in cons))}
 
 
+# ---- per-piece comparison of the stage buffers (mixed instances) -----------------------------
+BLOCK_KEYS = ("R", "Xinv", "P", "R2", "pred_dX", "pred_dY", "corr_dX", "corr_dY", "X+", "Y+")
+CLUSTER_KEYS = ("d", "pred_dx", "corr_dx", "x+")
+
+
+def stage_pieces(bi):
+    """{key: [(piece, start, stop)]} for every key of :func:`stage_reference`: the slices of the
+    flat C-ABI buffers that belong to one block (``"j<j>l<l>"``: R, Xinv, P, R2, the dX / dY of
+    both directions, X+, Y+), one (r,s) slot of one block (``"j<j>l<l>r<r>s<s>"``: A_Y, one entry
+    per vector of the block, K = sum of its ranks), one cluster (``"j<j>"``: S with dim_S^2 entries, d, the dx of both directions and x+
+    with dim_S), or the whole buffer (``"all"``: Q, p, the dy, y+ and the scalars)."""
+    blk, ay, S, xs = [], [], [], []
+    ob = oa = oS = 0
+    for j in range(bi.J):
+        D = bi.dim_S[j]
+        S.append((f"j{j}", oS, oS + D * D))
+        oS += D * D
+        xs.append((f"j{j}", bi.x_indices[j], bi.x_indices[j + 1]))
+        for l in range(bi.L[j]):
+            n, K = bi.Y_blocksizes[j][l], bi.rank_sums[j][l][-1]
+            blk.append((f"j{j}l{l}", ob, ob + n * n))
+            ob += n * n
+            for r in range(bi.m[j]):
+                for s in range(r + 1):
+                    ay.append((f"j{j}l{l}r{r}s{s}", oa, oa + K))
+                    oa += K
+    out = {k: blk for k in BLOCK_KEYS}
+    out.update({k: xs for k in CLUSTER_KEYS})
+    out["S"], out["A_Y"] = S, ay
+    ny = bi.n_y
+    for k, n in (("Q", ny * ny), ("p", ny), ("pred_dy", ny), ("corr_dy", ny), ("y+", ny), ("mu", 1),
+                 ("beta_c", 1), ("alpha_p", 1), ("alpha_d", 1)):
+        out[k] = [("all", 0, n)]
+    return out
+
+
+def piecewise_err(got, ref, bi, scales=None):
+    """{(key, piece): rel_err} of the stage buffers ``got`` against ``ref`` (the dictionaries of
+    :func:`stage_device` and :func:`stage_reference`), every piece of :func:`stage_pieces`
+    relative to its own largest reference entry, so that an error confined to a small cluster is
+    not hidden under a large cluster's scale.  ``scales`` (:func:`residual_scales`) keeps the
+    floor of the residual buffers P, p, d, which are at round-off level once feasible."""
+    scales = scales or {}
+    out = {}
+    for key, pieces in stage_pieces(bi).items():
+        if key not in ref:
+            continue
+        g, r = np.asarray(got[key]).ravel(), np.asarray(ref[key]).ravel()
+        assert len(g) == len(r) == pieces[-1][2], (key, len(g), len(r), pieces[-1][2])
+        for piece, a, c in pieces:
+            out[(key, piece)] = rel_err(g[a:c], r[a:c], scales.get(key, 0.0))
+    return out
+
+
+def summarize_pieces(ref, bi, digits, count=384):
+    """Fixture records of the stage buffers per piece: {key: {piece: summarize(slice)}}."""
+    return {key: {piece: summarize(np.asarray(ref[key], dtype=object).ravel()[a:c], digits, count)
+                  for piece, a, c in pieces}
+            for key, pieces in stage_pieces(bi).items() if key in ref}
+
+
+def compare_pieces(got, recs, bi, scales=None):
+    """{(key, piece): compare_summary} of stage buffers against :func:`summarize_pieces` records."""
+    scales = scales or {}
+    out = {}
+    for key, pieces in stage_pieces(bi).items():
+        if key not in recs:
+            continue
+        g = np.asarray(got[key], dtype=object).ravel()
+        assert len(g) == pieces[-1][2], (key, len(g), pieces[-1][2])
+        for piece, a, c in pieces:
+            out[(key, piece)] = compare_summary(g[a:c], recs[key][piece], scales.get(key, 0.0))
+    return out
+
+
+def worst(errs, tol):
+    """(error / tolerance, key) of the worst piece of a {key: error} dictionary; ``tol`` a number
+    or a dictionary over the same keys."""
+    t = (lambda k: tol[k]) if isinstance(tol, dict) else (lambda k: tol)
+    return max(((v / t(k), k) for k, v in errs.items()), key=lambda q: q[0] if q[0] == q[0] else np.inf)
+
+
+# ---- mixed instances: pk.synth_mixed(specs, n_y, seed=7) --------------------------------------
+def _sp(m, deltas, N, ranks=None):
+    return dict(m=m, deltas=list(deltas), N=N, ranks=ranks)
+
+
+_R3 = [[(1, 2, 1, 3, 1, 2)[k % 6] for k in range(47)]]
+# (no sample has rank 0 in both blocks)
+_RZ = [[(0, 1, 2, 1)[k % 4] for k in range(79)],
+       [((1, 2)[k % 8 == 0] if k % 4 == 0 else (1, 0, 2)[k % 3]) for k in range(79)]]
+_MS = [_sp(1, [20], 39), _sp(1, [100], 199), _sp(1, [70], 139), _sp(1, [12], 23)]
+_MT = [_sp(1, [40], 79), _sp(1, [33], 65, [[2] * 65]), _sp(1, [24], 47, _R3), _sp(1, [40, 24], 79, _RZ)]
+MIXED = {
+    "M-S": (_MS, 24),
+    "M-S+": (_MS + [_sp(1, [140], 279)], 24),
+    "M-T": (_MT, 24),
+    "M-Q": (_MT, 140),
+    "M-m": ([_sp(1, [70], 139), _sp(2, [30, 20], 59), _sp(1, [100], 199)], 24),
+    "M-bS": ([_sp(3, [30], 59), _sp(1, [20], 39)], 16),
+    "M-Bs": ([_sp(1, [140], 150), _sp(1, [20], 39)], 16),
+    # the multi-word fixtures (tests/golden/make_stage_fixtures.py) and their split-form variants
+    "mixdd": ([_sp(1, [12], 23), _sp(1, [70], 139), _sp(1, [40, 24], 79, _RZ)], 70),
+    "mixdds": ([_sp(1, [12], 23), _sp(1, [40, 24], 79, _RZ)], 70),
+    "mixqd": ([_sp(1, [8], 15), _sp(1, [36], 71), _sp(2, [10, 6], 19)], 40),
+    "mixqds": ([_sp(1, [8], 15), _sp(2, [10, 6], 19)], 40),
+}
+_MIXED_STATES = {}
+
+
+def mixed_instance(pk, name):
+    specs, n_y = MIXED[name]
+    return pk.synth_mixed(specs, n_y, seed=7)
+
+
+def mixed_oracle_case(pk, oracle, name, iters_before=2):
+    """(cons, b, bi, state, nxt, it) of a mixed instance: the numpy oracle's state after
+    ``iters_before`` iterations from initial_point(.., 10, 10) and its next iteration, computed
+    once per instance and left unchanged."""
+    if name not in _MIXED_STATES:
+        cons, b = mixed_instance(pk, name)
+        bi = oracle.get_block_info(cons)
+        ar = oracle.Fp64()
+        prm = {k: oracle._param(ar, v) for k, v in oracle.DEFAULTS.items()}
+        state = oracle.initial_point(ar, bi, 10.0, 10.0)
+        for _ in range(iters_before):
+            state, _ = oracle.iteration(ar, cons, bi, b, None, ar.num(0), state, False, prm)
+        nxt, it = oracle.iteration(ar, cons, bi, b, None, ar.num(0), state, False, prm)
+        _MIXED_STATES[name] = (cons, b, bi, state, nxt, it)
+    return _MIXED_STATES[name]
+
+
 def _sample_sums(M, starts, counts):
     """Sums of the rows and columns of the K x K matrix M over the rank groups of the samples
     (N x N): group k holds rows starts[k] .. starts[k] + counts[k] - 1 (none when the rank is 0)."""
@@ -320,13 +452,13 @@ def sample_indices(n, count=384, seed=2024):
     return sorted(s)
 
 
-def summarize(arr, digits):
-    """Fixture record of a flat buffer: sampled entries, two +-1 sketches, the l1 norm and the
-    max |entry| (decimal strings at ``digits`` significant digits)."""
+def summarize(arr, digits, count=384):
+    """Fixture record of a flat buffer: sampled entries (``count`` + 64 of them), two +-1
+    sketches, the l1 norm and the max |entry| (decimal strings at ``digits`` significant digits)."""
     import mpmath
     a = [mpmath.mpf(v) for v in np.asarray(arr, dtype=object).ravel()]
     n = len(a)
-    idx = sample_indices(n)
+    idx = sample_indices(n, count)
     st = lambda v: mpmath.nstr(v, digits, strip_zeros=False, min_fixed=1, max_fixed=0)
     rec = {"n": n, "idx": idx, "val": [st(a[i]) for i in idx],
            "l1": st(mpmath.fsum(abs(v) for v in a)), "amax": st(max([abs(v) for v in a] + [mpmath.mpf(0)]))}

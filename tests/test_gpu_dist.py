@@ -22,13 +22,19 @@ def _port():
     return p
 
 
-@pytest.mark.parametrize("backend,J", [("gloo", 5), ("rccl", 5), ("gloo", 1)])
+@pytest.mark.parametrize("backend,J", [("gloo", 5), ("rccl", 5), ("gloo", 1), ("gloo", "mixed")])
 def test_two_ranks_match_single_rank(pk, backend, J):
     """backend "rccl": the native communicator cannot put two ranks on the box's one GPU (RCCL
     refuses with "invalid usage" on every rank), so this also covers the agreed fallback to the
     host-staged exchange; on a multi-GPU node the same worker runs the native all-gathers.
     J = 1: one rank owns no cluster (as config 5's 7 clusters on 8 GPUs) and only contributes
-    neutral partials."""
+    neutral partials.
+    J = "mixed": the M-T instance of helpers.MIXED (a rank-1, an all-rank-2, an unequal-rank and
+    an L = 2 cluster, n_y = 24) with the ownership {0, 2} | {1, 3} set by the worker (the
+    balancer's own split of it is the contiguous {0, 1} | {2, 3}): each shard is a non-contiguous
+    subset of the clusters and the plan flags differ per rank -- rank 0 holds the direct cluster
+    and one gsum cluster and no grp2 cluster (the fused Schur kernel, plain template), rank 1 the
+    grp2 cluster and the L = 2 gsum cluster (any_grp2 beside grp = 1: the unfused pair)."""
     iters = 4
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "r")
@@ -39,8 +45,14 @@ def test_two_ranks_match_single_rank(pk, backend, J):
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         res = [json.load(open(f"{out}.{k}.json")) for k in range(2)]
-    cons, b = pk.synth(seed=12, J=J, delta=16, rank=1, n_y=9, m=1)
+    if J == "mixed":
+        from helpers import mixed_instance
+        cons, b = mixed_instance(pk, "M-T")
+    else:
+        cons, b = pk.synth(seed=12, J=J, delta=16, rank=1, n_y=9, m=1)
     bi = pk.get_block_info(cons)
+    if J == "mixed":
+        assert sorted(sorted(rr["owned"]) for rr in res) == [[0, 2], [1, 3]]
     dev = pk.DeviceSolver(cons, b, bi)
     P = pk.make_params("0.3", "0.1", "0.7", 0)
     dev.set_state(*pk.initial_point(bi, 10.0, 10.0))
