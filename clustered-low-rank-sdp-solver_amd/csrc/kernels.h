@@ -2107,6 +2107,21 @@ __global__ __launch_bounds__(256) void perm_rows(const PermDesc<T>* __restrict__
 // compute_step_length (MPMP.jl:1857-1870), which returns the same spectrum for the
 // (mathematically symmetric) L^-1 dM L^-T.
 // ------------------------------------------------------------------------------------------
+// exact power-of-two scaling of every limb
+__device__ inline double scale2(double v, int e) { return ldexp(v, e); }
+__device__ inline mw::dd scale2(const mw::dd& v, int e) { return mw::dd(ldexp(v.hi, e), ldexp(v.lo, e)); }
+__device__ inline mw::qd scale2(const mw::qd& v, int e) {
+  return mw::qd(ldexp(v.x[0], e), ldexp(v.x[1], e), ldexp(v.x[2], e), ldexp(v.x[3], e));
+}
+// Input scaling of the eigen-solvers: ex with mx = f 2^ex, 1/2 <= f < 1, for the largest
+// leading-limb magnitude mx of a block (0 for a zero or non-finite one).  The block is divided by
+// 2^ex when it is loaded and lambda_min multiplied back (exact), so the squares the reflectors
+// form (sum x_i^2, alpha^2) neither overflow nor flush to zero whatever the block's norm, as
+// eigmin_split's ex0.
+__device__ inline int pow2_exp(double mx) {
+  return mx > 0.0 && mx < INFINITY ? __builtin_amdgcn_frexp_exp(mx) : 0;
+}
+
 template <class T>
 __device__ __forceinline__ int sturm_count(const T* dg, const T* e2, int n, T sigma) {
   int cnt = 0;
@@ -2132,13 +2147,20 @@ __global__ __launch_bounds__(256) void eigmin_batched(const MatDesc<T>* __restri
   T* e2 = dg + n;                          // n   squared off-diagonal
   T* red = e2 + n;                         // blockDim.x
   T* A = d.A;
-  // symmetrise: A = (A + A^T) / 2
+  // the power of two of the largest entry (pow2_exp)
+  double amax = 0.0;
+  for (int e = tid; e < n * n; e += blockDim.x)
+    amax = fmax(amax, fabs(Num<T>::hi(A[e % n + (size_t)(e / n) * lda])));
+  const int ex = pow2_exp(block_max(amax, reinterpret_cast<double*>(red)));
+  // symmetrise and scale: A = (A + A^T) / 2^(ex + 1)
   for (int e = tid; e < n * n; e += blockDim.x) {
     const int i = e % n, j = e / n;
     if (i > j) {
-      const T s = (A[i + (size_t)j * lda] + A[j + (size_t)i * lda]) * T(0.5);
+      const T s = (scale2(A[i + (size_t)j * lda], -ex) + scale2(A[j + (size_t)i * lda], -ex)) * T(0.5);
       A[i + (size_t)j * lda] = s;
       A[j + (size_t)i * lda] = s;
+    } else if (i == j) {
+      A[i + (size_t)i * lda] = scale2(A[i + (size_t)i * lda], -ex);
     }
   }
   __syncthreads();
@@ -2237,7 +2259,7 @@ __global__ __launch_bounds__(256) void eigmin_batched(const MatDesc<T>* __restri
       lo = nlo;
       hi = nhi;
     }
-    if (tid == 0) out[blockIdx.x] = (lo + hi) * T(0.5);
+    if (tid == 0) out[blockIdx.x] = scale2((lo + hi) * T(0.5), ex);
   }
 }
 

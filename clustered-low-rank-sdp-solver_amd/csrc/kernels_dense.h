@@ -1289,11 +1289,19 @@ __device__ inline T lane0_sum_mw(T v, int m) {
   return v;
 }
 
-// exact power-of-two scaling of every limb
-__device__ inline double scale2(double v, int e) { return ldexp(v, e); }
-__device__ inline mw::dd scale2(const mw::dd& v, int e) { return mw::dd(ldexp(v.hi, e), ldexp(v.lo, e)); }
-__device__ inline mw::qd scale2(const mw::qd& v, int e) {
-  return mw::qd(ldexp(v.x[0], e), ldexp(v.x[1], e), ldexp(v.x[2], e), ldexp(v.x[3], e));
+// (scale2, the exact power-of-two scaling of every limb: kernels.h)
+// pow2_exp of a block from every thread's largest loaded magnitude (NW waves; red: NW doubles
+// of LDS).  Its barrier also orders the load of the image before the reads that follow.
+template <int NW>
+__device__ __forceinline__ int load_scale_exp(double amax, double* __restrict__ red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  double mx = red[0];
+#pragma unroll
+  for (int q = 1; q < NW; ++q) mx = fmax(mx, red[q]);
+  return pow2_exp(mx);
 }
 // The half-width word of a multi-word type and the rounding to it (the leading words of the
 // non-overlapping representation).
@@ -1370,14 +1378,15 @@ __device__ __forceinline__ bool sturm_any_below_mw(const T* __restrict__ dg, con
 #endif
 // The multisection phase of eigmin_lds / eigmin_lds2 (512 threads): lambda_min of the
 // tridiagonal (dg, e2 = squared off-diagonals) in LDS to the word's precision, into
-// out[blockIdx.x].  A is LDS scratch (>= 2n + 14 doubles), Wv one word of LDS scratch.
+// out[blockIdx.x], times 2^ex (the input scaling of the caller, pow2_exp).  A is LDS scratch
+// (>= 2n + 14 doubles), Wv one word of LDS scratch.
 template <class T, bool NEWTON>
 __device__ __forceinline__ void eig_multisection(const T* __restrict__ dg, const T* __restrict__ e2, int n,
-                                 T* __restrict__ A, T* __restrict__ Wv, T* __restrict__ out) {
+                                 T* __restrict__ A, T* __restrict__ Wv, T* __restrict__ out, int ex) {
   constexpr int NT = 512, NW = 8;
   const int tid = threadIdx.x;
   if (n == 1) {
-    if (tid == 0) out[blockIdx.x] = dg[0];
+    if (tid == 0) out[blockIdx.x] = scale2(dg[0], ex);
     return;
   }
   // ---- multisection, 256-way on waves 0-3 (8 bits per round), in two phases:
@@ -1556,7 +1565,7 @@ __device__ __forceinline__ void eig_multisection(const T* __restrict__ dg, const
     const bool ok = masks[0] && masks[1];
     __syncthreads();
     if (ok) {
-      if (tid == 0) out[blockIdx.x] = s;
+      if (tid == 0) out[blockIdx.x] = scale2(s, ex);
       return;
     }
   }
@@ -1609,7 +1618,7 @@ __device__ __forceinline__ void eig_multisection(const T* __restrict__ dg, const
       }
     }
   }
-  if (tid == 0) out[blockIdx.x] = (lo + hi) * T(0.5);
+  if (tid == 0) out[blockIdx.x] = scale2((lo + hi) * T(0.5), ex);
 }
 
 template <class T, bool NEWTON = true>
@@ -1630,20 +1639,26 @@ __global__ __launch_bounds__(512) void eigmin_lds(const MatDesc<T>* __restrict__
   T* p = v + n;                            // NC * n partials (eig_lds_bytes)
   T* dg = p + NC * n;                      // n
   T* e2 = dg + n;                          // n
-  // coalesced load, then symmetrise in LDS: A = (A + A^T)/2
+  T* Wv = e2 + n;        // w vector (n)            -- carved after e2
+  T* scal = Wv + n;      // [0] = beta, [1] = tail flag
+  T* redw = scal + 4;    // NW partials of v^T A' v
+  // coalesced load, then symmetrise and scale in LDS: A = (A + A^T) / 2^(ex + 1) (pow2_exp)
+  double amax = 0.0;
   for (int j = tid >> 6; j < n; j += NT / 64)
-    for (int i = tid & 63; i < n; i += 64) A[i + (size_t)j * n] = d.A[i + (size_t)j * d.lda];
-  __syncthreads();
+    for (int i = tid & 63; i < n; i += 64) {
+      // (the leading limb read back from the image: a local copy of the word kept a quad-double
+      // in scratch)
+      A[i + (size_t)j * n] = d.A[i + (size_t)j * d.lda];
+      amax = fmax(amax, fabs(Num<T>::hi(A[i + (size_t)j * n])));
+    }
+  const int ex = load_scale_exp<NW>(amax, reinterpret_cast<double*>(redw));
   for (int j = tid >> 6; j < n; j += NT / 64)
-    for (int i = tid & 63; i < j; i += 64) {
-      const T sv = (A[i + (size_t)j * n] + A[j + (size_t)i * n]) * T(0.5);
+    for (int i = tid & 63; i <= j; i += 64) {
+      const T sv = (scale2(A[i + (size_t)j * n], -ex) + scale2(A[j + (size_t)i * n], -ex)) * T(0.5);
       A[i + (size_t)j * n] = sv;
       A[j + (size_t)i * n] = sv;
     }
   __syncthreads();
-  T* Wv = e2 + n;        // w vector (n)            -- carved after e2
-  T* scal = Wv + n;      // [0] = beta, [1] = tail flag
-  T* redw = scal + 4;    // NW partials of v^T A' v
   for (int k = 0; k + 2 < n; ++k) {
     const int m = n - k - 1;
     T* Ak = A + (k + 1) + (size_t)(k + 1) * n;  // trailing m x m, ld n
@@ -1744,7 +1759,7 @@ __global__ __launch_bounds__(512) void eigmin_lds(const MatDesc<T>* __restrict__
     }
   }
   __syncthreads();
-  eig_multisection<T, NEWTON>(dg, e2, n, A, Wv, out);
+  eig_multisection<T, NEWTON>(dg, e2, n, A, Wv, out, ex);
   EIG_STAMP(6)
 }
 
@@ -1957,19 +1972,23 @@ __device__ __forceinline__ void eigmin_lds2_dev(const MatDesc<T>& d, T* __restri
   T* e2 = dg + n;                              // n
   T* scal = e2 + n;                            // [0..1] beta of the two v buffers
   T* redw = scal + 4;                          // 2 x 8 per-wave parts of v^T p
-  // coalesced load, then symmetrise: A = (A + A^T)/2
+  // coalesced load, then symmetrise and scale: A = (A + A^T) / 2^(ex + 1) (pow2_exp)
+  double amax = 0.0;
   for (int j = tid >> 6; j < n; j += NT / 64)
-    for (int i = lane; i < n; i += 64) A[i + (size_t)j * ld] = d.A[i + (size_t)j * d.lda];
-  __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+      A[i + (size_t)j * ld] = d.A[i + (size_t)j * d.lda];
+      amax = fmax(amax, fabs(Num<T>::hi(A[i + (size_t)j * ld])));
+    }
+  const int ex = load_scale_exp<NT / 64>(amax, reinterpret_cast<double*>(redw));
   for (int j = tid >> 6; j < n; j += NT / 64)
-    for (int i = lane; i < j; i += 64) {
-      const T sv = (A[i + (size_t)j * ld] + A[j + (size_t)i * ld]) * T(0.5);
+    for (int i = lane; i <= j; i += 64) {
+      const T sv = (scale2(A[i + (size_t)j * ld], -ex) + scale2(A[j + (size_t)i * ld], -ex)) * T(0.5);
       A[i + (size_t)j * ld] = sv;
       A[j + (size_t)i * ld] = sv;
     }
   __syncthreads();
   if (n == 1) {
-    if (tid == 0) out[blockIdx.x] = A[0];
+    if (tid == 0) out[blockIdx.x] = scale2(A[0], ex);
     return;
   }
   tridiag_lds2<T, false>(A, ld, n, vb, p, dg, e2, scal, redw, nullptr, nullptr, nullptr);
@@ -1977,7 +1996,7 @@ __device__ __forceinline__ void eigmin_lds2_dev(const MatDesc<T>& d, T* __restri
     if (tid == 0) out[blockIdx.x] = dg[n - 1] + e2[0];
     return;
   }
-  eig_multisection<T, true>(dg, e2, n, A, p, out);
+  eig_multisection<T, true>(dg, e2, n, A, p, out, ex);
 }
 
 // redo (eigmin_mx's fallback launch): only the blocks with redo[block] != 0

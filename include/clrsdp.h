@@ -322,7 +322,12 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
  * the eigenvalue part of compute_step_length (MPMP.jl:1857-1870, approx_eig_qr! of L^-1 dM L^-T),
  * Householder tridiagonalisation + Sturm multisection (+ the multi-word Newton tail) as the
  * loop body runs it.  A: the nblocks blocks of sizes n[] concatenated column-major, as `words`
- * planes of doubles (hi limb first; the blocks must be exactly symmetric); min_eig: `words` planes of nblocks values. */
+ * planes of doubles (hi limb first; the blocks must be exactly symmetric); min_eig: `words` planes of nblocks values.
+ * 1 <= n[b] <= 4096.  Scale: each block is divided by the power of two of its largest leading-limb
+ * magnitude on load and lambda_min multiplied back (exact), so the result is relative to the
+ * block's norm at any scale; supported (and tested) for blocks whose largest |entry| lies in
+ * [2^-600, 2^600].  Outside it the trailing limbs of a multi-word entry or of the result can
+ * fall into the subnormal range and the accuracy degrades towards fp64's. */
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                       const double* A, double* min_eig);
 

@@ -427,6 +427,59 @@ def cw_err(got, ref, bound):
                           for x, y, s in zip(g, r, bd)] + [mpmath.mpf(0)]))
 
 
+# ---- eigenvalue references without an eigen-solve ---------------------------------------------
+def known_spectrum(n, lam, rng, reflectors=3):
+    """Symmetric n x n object array of 320-bit mpmath numbers with the eigenvalues ``lam``:
+    H_r .. H_1 diag(lam) H_1 .. H_r with H = I - 2 u u^T / u^T u and u random (float64 entries).
+    Each reflector is applied as the symmetric rank-2 update A - u w^T - w u^T (p = beta A u,
+    K = beta u^T p / 2, w = p - K u), O(n^2) per reflector.  The lower triangle is copied over the
+    upper one (the roundings leave ~1e-97 of asymmetry).  lambda_min is min(lam) by construction,
+    to the 320-bit rounding of O(n) orthogonal updates (~n 2^-320 ||A||)."""
+    import mpmath
+    assert len(lam) == n
+    with mpmath.workprec(320):
+        A = np.empty((n, n), dtype=object)
+        A[...] = mpmath.mpf(0)
+        for i in range(n):
+            A[i, i] = mpmath.mpf(lam[i])
+        for _ in range(reflectors if n > 1 else 0):
+            u = np.array([mpmath.mpf(float(x)) for x in rng.standard_normal(n)], dtype=object)
+            beta = 2 / mpmath.fsum(x * x for x in u)
+            p = A.dot(u) * beta
+            K = beta * mpmath.fsum(x * y for x, y in zip(u, p)) / 2
+            w = p - K * u
+            A = A - np.outer(u, w) - np.outer(w, u)
+        il = np.tril_indices(n, -1)
+        A[(il[1], il[0])] = A[il]
+    return A
+
+
+def neg_pivots(M):
+    """Number of negative pivots of the L D L^T factorisation without pivoting of the symmetric
+    matrix M (object array of mpmath numbers or floats; only the lower triangle is read), at 320
+    bits.  By Sylvester's law of inertia that is the number of negative eigenvalues of M, and for
+    M = dM - sigma B with B positive definite the number of generalised eigenvalues of (dM, B)
+    below sigma.  A zero pivot is refused (the count would be undefined)."""
+    import mpmath
+    n = len(M)
+    with mpmath.workprec(320):
+        A = np.empty((n, n), dtype=object)
+        A[...] = mpmath.mpf(0)
+        for i in range(n):
+            for j in range(i + 1):
+                A[i, j] = mpmath.mpf(M[i][j])
+        neg = 0
+        for k in range(n):
+            d = A[k, k]
+            assert d != 0, f"neg_pivots: zero pivot {k}"
+            neg += d < 0
+            col = A[k + 1:, k]
+            # (the whole outer product in one numpy call is faster than row slices of its
+            # lower triangle: 1.6 s against 2.3 s at n = 100)
+            A[k + 1:, k + 1:] -= np.tril(np.outer(col / d, col))
+    return int(neg)
+
+
 # ---- sampled fixtures of large stage outputs (tests/golden/make_stage_fixtures.py) ----------
 SKETCH_MULT = (0x9E3779B1, 0x85EBCA77)
 
