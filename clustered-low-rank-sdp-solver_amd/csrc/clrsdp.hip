@@ -512,17 +512,36 @@ void GemmPlan<T>::launch_uni_impl(hipStream_t s, double alpha, double beta, cons
   }
 }
 
+// CLRSDP_TRSM_BLK: unset = trsm_batched wherever its panel fits in LDS and the blocked chain
+// across workgroups beyond; 1 the chain at every size trsm_batched would have served; 0
+// trsm_batched only (larger matrices: E_ARG)
+inline int trsm_blk_mode() {
+  return env_off("CLRSDP_TRSM_BLK") ? 0 : env_on("CLRSDP_TRSM_BLK") ? 1 : -1;
+}
+
 template <class T>
 struct TrsmPlan : PlanBase {
   // NC: right-hand sides per workgroup.  Multi-word solves with many right-hand sides
   // (W = L^-1 B) take 16 (one diagonal pass of 256 threads, and four times the workgroups of 64:
   // the panel update's multi-word products spread over more CUs).
   static constexpr int NB = 16, NCW = 64, NCN = 16;
-  // LDS of the LU-mode solves (modes 1 and 2) at n: launch()'s dynamic diagonal block, solved
-  // rows and panel, and the kernel's static reciprocals.  This is the size bound of the LU path.
+  // LDS of trsm_batched at n: launch()'s dynamic diagonal block, solved rows and panel, and the
+  // kernel's static reciprocals.  Beyond LDS_MAX (fp64 n > 1199, dd 559, qd 239) the plan takes
+  // the blocked chain: super-blocks of kb rows, each solved by trsm_batched on the sub-triangle
+  // (per-step descriptors) and followed by trsm_blk_update on the rows not yet solved.
   static constexpr size_t lu_lds_bytes(int n) {
     return sizeof(T) * ((size_t)NB * NB + (size_t)NB * NCW + (size_t)NB * n + NB);
   }
+  static bool one_cu_fits(int n) { return lu_lds_bytes(n) <= LDS_MAX; }
+  // the chain's super-block height (CLRSDP_TRSM_KB overrides; rounded down to a multiple of NB
+  // that fits the panel): DESIGN.md §3 has the sweep
+  static constexpr int KB_DEFAULT = 128;
+  bool blk = false;
+  int kb = 0;
+  struct Step { TrsmDesc<T>* d; int* dt; unsigned grid; };
+  std::vector<Step> steps;  // by super-block, top down
+  // update tiles: TR rows x UC right-hand sides (vector solves: one column, no padding)
+  static constexpr int TR = 64, UC = 16;
   std::vector<TrsmDesc<T>> h;
   std::vector<int> t2d;
   TrsmDesc<T>* d = nullptr;
@@ -571,13 +590,31 @@ struct TrsmPlan : PlanBase {
         lds_attr_once(a64[3], (const void*)trsv_wave<T, false, NCV16>, (int)trsv_wave_lds<T>());
       }
     }
-    if (mode != 0 && lu_lds_bytes(nmax) > 64 * 1024) {  // (outside any graph capture)
-      if (lu_lds_bytes(nmax) > LDS_MAX)
-        throw ClrsdpError{CLRSDP_E_ARG, "LU triangular solve: matrix too large for the on-chip panel"};
-      static std::atomic<unsigned long long> alu[3];
-      lds_attr_once(alu[0], (const void*)trsm_batched<T, false, NB, NCW, 256, true, false>, (int)(LDS_MAX - 1024));
-      lds_attr_once(alu[1], (const void*)trsm_batched<T, true, NB, NCW, 256, false, true>, (int)(LDS_MAX - 1024));
-      lds_attr_once(alu[2], (const void*)trsm_batched<T, false, NB, NCW, 256, false, true>, (int)(LDS_MAX - 1024));
+    const int bm = trsm_blk_mode();
+    blk = !vec && (bm == 1 || (bm < 0 && !one_cu_fits(nmax)));
+    if (!vec && !blk && !one_cu_fits(nmax))
+      throw ClrsdpError{CLRSDP_E_ARG, "triangular solve: matrix too large for the on-chip panel of trsm_batched (CLRSDP_TRSM_BLK=0)"};
+    if (blk) {
+      int kmax = NB;
+      while (one_cu_fits(kmax + NB)) kmax += NB;
+      long k = env_int("CLRSDP_TRSM_KB", KB_DEFAULT);
+      k = std::max<long>(NB, std::min<long>(k, kmax)) / NB * NB;
+      kb = (int)k;
+    }
+    const int npan = blk ? std::min(kb, nmax) : nmax;  // rows of the largest on-chip solve
+    if (lu_lds_bytes(npan) > 64 * 1024) {  // (outside any graph capture)
+      static std::atomic<unsigned long long> alu[10];
+      const void* fns[10] = {(const void*)trsm_batched<T, false, NB, NCW, 256, true, false>,
+                            (const void*)trsm_batched<T, true, NB, NCW, 256, true, false>,
+                            (const void*)trsm_batched<T, true, NB, NCW, 256, false, true>,
+                            (const void*)trsm_batched<T, false, NB, NCW, 256, false, true>,
+                            (const void*)trsm_batched<T, false, NB, NCN, 256>,
+                            (const void*)trsm_batched<T, true, NB, NCN, 256>,
+                            (const void*)trsm_batched<T, false, NB, NCW, 1024>,
+                            (const void*)trsm_batched<T, true, NB, NCW, 1024>,
+                            (const void*)trsm_batched<T, false, NB, NCW>,
+                            (const void*)trsm_batched<T, true, NB, NCW>};
+      for (int q = mode != 0 ? 0 : 4; q < (mode != 0 ? 4 : 10); ++q) lds_attr_once(alu[q], fns[q], (int)(LDS_MAX - 1024));
     }
     if (!vec_rhs())
       for (TrsmDesc<T>& t : h) { t.pad = 0; t.src = nullptr; }  // (the caller fills B)
@@ -588,6 +625,24 @@ struct TrsmPlan : PlanBase {
     }
     d = own(h);
     dt = own(t2d);
+    steps.clear();
+    if (!blk) return;
+    // per super-block: the sub-triangles of the matrices that reach it
+    for (int k0 = 0; k0 < nmax; k0 += kb) {
+      std::vector<TrsmDesc<T>> hs;
+      std::vector<int> ts;
+      for (const TrsmDesc<T>& t : h) {
+        if (t.n <= k0) continue;
+        TrsmDesc<T> u = t;
+        u.L = t.L + k0 + (size_t)k0 * t.ldl;
+        u.B = t.B + k0;
+        u.n = std::min(kb, t.n - k0);
+        u.tile0 = (int)ts.size();
+        for (int i = 0; i < (int)cdiv(u.nrhs, nc); ++i) ts.push_back((int)hs.size());
+        hs.push_back(u);
+      }
+      steps.push_back(Step{own(hs), own(ts), (unsigned)ts.size()});
+    }
   }
   void launch_vec(hipStream_t s, bool trans, unsigned grid) const {
     if constexpr (!std::is_same<T, double>::value) {
@@ -616,9 +671,47 @@ struct TrsmPlan : PlanBase {
   int mode = 0;
   void launch(hipStream_t s, bool trans) const {
     if (h.empty()) return;
+    if (!blk) {
+      launch_tb(s, trans, d, dt, (unsigned)t2d.size(), nmax);
+      return;
+    }
+    // the blocked chain: forward top-down, trans bottom-up; constant launch arguments, so the
+    // loop is capture-safe
+    const int ns = (int)steps.size();
+    const unsigned nm = (unsigned)h.size();
+    for (int q = 0; q < ns; ++q) {
+      const int si = trans ? ns - 1 - q : q, k0 = si * kb;
+      launch_tb(s, trans, steps[si].d, steps[si].dt, steps[si].grid, std::min(kb, nmax - k0));
+      const int nr = trans ? k0 : nmax - k0 - kb;  // rows still to be solved (largest matrix)
+      if (nr <= 0) continue;
+      const int ntr = (int)cdiv(nr, TR);
+      if (rmax == 1) {
+        const dim3 g((unsigned)ntr, nm);
+        if (trans) {
+          if (mode == 2) trsm_blk_update<T, true, true, NB, TR, 1, TR><<<g, TR, 0, s>>>(d, k0, kb, ntr);
+          else trsm_blk_update<T, true, false, NB, TR, 1, TR><<<g, TR, 0, s>>>(d, k0, kb, ntr);
+        } else {
+          if (mode == 2) trsm_blk_update<T, false, true, NB, TR, 1, TR><<<g, TR, 0, s>>>(d, k0, kb, ntr);
+          else trsm_blk_update<T, false, false, NB, TR, 1, TR><<<g, TR, 0, s>>>(d, k0, kb, ntr);
+        }
+      } else {
+        const dim3 g((unsigned)ntr * cdiv(rmax, UC), nm);
+        if (trans) {
+          if (mode == 2) trsm_blk_update<T, true, true, NB, TR, UC, 256><<<g, 256, 0, s>>>(d, k0, kb, ntr);
+          else trsm_blk_update<T, true, false, NB, TR, UC, 256><<<g, 256, 0, s>>>(d, k0, kb, ntr);
+        } else {
+          if (mode == 2) trsm_blk_update<T, false, true, NB, TR, UC, 256><<<g, 256, 0, s>>>(d, k0, kb, ntr);
+          else trsm_blk_update<T, false, false, NB, TR, UC, 256><<<g, 256, 0, s>>>(d, k0, kb, ntr);
+        }
+      }
+      HIPCHK(hipGetLastError());
+    }
+  }
+  // one trsm_batched launch over descriptors d / tiles dt with at most nmax rows
+  void launch_tb(hipStream_t s, bool trans, const TrsmDesc<T>* d, const int* dt, unsigned grid,
+                 int nmax) const {
     constexpr int NC = NCW;
     const size_t lds = sizeof(T) * ((size_t)NB * NB + (size_t)NB * NC + (size_t)NB * nmax);
-    const unsigned grid = (unsigned)t2d.size();
     if constexpr (!std::is_same<T, double>::value) {
       if (vec && mode == 0) {
         launch_vec(s, trans, grid);
@@ -633,8 +726,9 @@ struct TrsmPlan : PlanBase {
       HIPCHK(hipGetLastError());
       return;
     }
-    if (mode == 1 && !trans) {
-      trsm_batched<T, false, NB, NC, 256, true, false><<<grid, 256, lds, s>>>(d, dt);
+    if (mode == 1) {  // (the solver's LU path solves with L forward only; clrsdp_trsm both ways)
+      if (trans) trsm_batched<T, true, NB, NC, 256, true, false><<<grid, 256, lds, s>>>(d, dt);
+      else trsm_batched<T, false, NB, NC, 256, true, false><<<grid, 256, lds, s>>>(d, dt);
       HIPCHK(hipGetLastError());
       return;
     }
@@ -2036,10 +2130,10 @@ struct Solver final : HandleBase {
   //   solves:  t_j = L_j^-1 rhs_j[perm_j]; u = sum_j W2_j^T t_j; dy = U_Q^-1 L_Q^-1 (p - u)[perm];
   //            dx_j = U_j^-1 (t_j + W1_j dy)                                  (MPMP.jl:1743-1776)
   //   X^-1:    X_b[perm_b] = L_b U_b; X_b^-1 = U_b^-1 L_b^-1 (P_b I)          (approx_inv!, 781)
-  // The factorisation itself has no size bound (the blocked chain takes over beyond the on-chip
-  // panel of getrf_batched: fp64 624, dd 312, qd 156) unless CLRSDP_LU_BLK=0 keeps getrf_batched
-  // alone.  What bounds the LU path is the panel of its triangular solves (trsm_batched modes 1
-  // and 2, TrsmPlan::launch): fp64 n <= 1200, dd 560, qd 240.
+  // Neither the factorisation nor its triangular solves have a size bound: beyond the on-chip
+  // panels (getrf_batched: fp64 624, dd 312, qd 156; trsm_batched: fp64 1199, dd 559, qd 239) the
+  // blocked chains across workgroups take over, unless CLRSDP_LU_BLK=0 / CLRSDP_TRSM_BLK=0 keep
+  // the on-chip kernels alone.
   int lu_nmax() const {
     int nmax = (int)n_y;
     for (int c = 0; c < nc(); ++c) nmax = std::max(nmax, (int)Ds[oc[c]]);
@@ -2049,13 +2143,13 @@ struct Solver final : HandleBase {
   bool lu_fits() const {
     const int nmax = lu_nmax();
     if (lu_blk_mode() == 0 && !LuPlan<T>::one_cu_fits(nmax)) return false;
-    return TrsmPlan<T>::lu_lds_bytes(nmax) <= LDS_MAX;
+    return trsm_blk_mode() != 0 || TrsmPlan<T>::one_cu_fits(nmax);
   }
   void build_lu_plans() {
     if (lu_built) return;
     if (!lu_fits()) {
-      if (TrsmPlan<T>::lu_lds_bytes(lu_nmax()) > LDS_MAX)
-        throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of the LU triangular solves"};
+      if (trsm_blk_mode() == 0 && !TrsmPlan<T>::one_cu_fits(lu_nmax()))
+        throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of the LU triangular solves (CLRSDP_TRSM_BLK=0)"};
       throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of getrf_batched (CLRSDP_LU_BLK=0)"};
     }
     try {
@@ -3691,6 +3785,45 @@ void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t
     for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
 }
 
+// Triangular solves of each block at the word type T through TrsmPlan, as the solver runs them
+// (trsv_wave / trsm_batched, or the blocked chain beyond the on-chip panel / with
+// CLRSDP_TRSM_BLK=1): planes in, B planes in and out
+template <class T>
+void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n, const int64_t* nrhs,
+                const double* Ap, double* Bp) {
+  constexpr int W = Num<T>::W;
+  std::vector<int64_t> off(nblk + 1, 0), boff(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    off[b + 1] = off[b] + n[b] * n[b];
+    boff[b + 1] = boff[b] + n[b] * nrhs[b];
+  }
+  DeviceGuard dg(device);
+  const int64_t tot = off[nblk], totb = boff[nblk];
+  std::vector<double> h((size_t)tot * W), hb((size_t)totb * W);
+  for (int64_t e = 0; e < tot; ++e)
+    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
+  for (int64_t e = 0; e < totb; ++e)
+    for (int q = 0; q < W; ++q) hb[(size_t)e * W + q] = Bp[(size_t)q * totb + e];
+  DevBuf mem;
+  T* A = mem.alloc<T>(tot);
+  T* B = mem.alloc<T>(totb);
+  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(B, hb.data(), (size_t)totb * sizeof(T), hipMemcpyHostToDevice));
+  TrsmPlan<T> tp;
+  tp.mode = mode;
+  for (int64_t b = 0; b < nblk; ++b)
+    tp.add(A + off[b], (int)n[b], B + boff[b], (int)n[b], (int)n[b], (int)nrhs[b]);
+  tp.finalize();
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  tp.launch(s, trans != 0);
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(hb.data(), B, (size_t)totb * sizeof(T), hipMemcpyDeviceToHost));
+  for (int64_t e = 0; e < totb; ++e)
+    for (int q = 0; q < W; ++q) Bp[(size_t)q * totb + e] = hb[(size_t)e * W + q];
+}
+
 int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh, const double* dMh,
                     double gamma, double* alpha, double* min_eig, std::string& err) {
   DeviceGuard dg(device);
@@ -3986,6 +4119,29 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
     if (words == 1) getrf_words<double>(device, nblocks, n, A, perm, info);
     else if (words == 2) getrf_words<mw::dd>(device, nblocks, n, A, perm, info);
     else getrf_words<mw::qd>(device, nblocks, n, A, perm, info);
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans, int64_t nblocks,
+                    const int64_t* n, const int64_t* nrhs, const double* A, double* B) {
+  if (nblocks <= 0 || !n || !nrhs || !A || !B) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
+  if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  if (mode < 0 || mode > 2) { g_last_error = "mode must be 0, 1 or 2"; return CLRSDP_E_ARG; }
+  for (int64_t b = 0; b < nblocks; ++b) {
+    if (n[b] <= 0 || n[b] > 4096) { g_last_error = "block size out of range"; return CLRSDP_E_ARG; }
+    if (nrhs[b] <= 0 || nrhs[b] > 4096) { g_last_error = "number of right-hand sides out of range"; return CLRSDP_E_ARG; }
+  }
+  try {
+    if (words == 1) trsm_words<double>(device, mode, trans, nblocks, n, nrhs, A, B);
+    else if (words == 2) trsm_words<mw::dd>(device, mode, trans, nblocks, n, nrhs, A, B);
+    else trsm_words<mw::qd>(device, mode, trans, nblocks, n, nrhs, A, B);
     return CLRSDP_OK;
   } catch (const ClrsdpError& e) {
     g_last_error = e.msg;

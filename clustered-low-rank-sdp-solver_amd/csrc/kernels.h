@@ -11,8 +11,9 @@
 //   gemv_batched    the N = 1 products
 //   potrf_batched   in-place lower Cholesky              (spd_inv!/cho!/approx_lu! replacements;
 //                   the sizes beyond kernels_dense.h's on-chip factorisations)
-//   trsm_batched, trsv_wave, trsv_wave128
-//                   B <- L^-1 B  or  L^-T B              (approx_solve_tril!/triu!)
+//   trsm_batched, trsv_wave, trsv_wave128, trsm_blk_update
+//                   B <- L^-1 B  or  L^-T B              (approx_solve_tril!/triu!; the last: the
+//                   update of the blocked chain beyond trsm_batched's on-chip panel)
 //   getrf_batched, getrf_blk_*
 //                   pivoted LU in place                  (approx_lu! / approx_inv!, the fallback)
 //   eigmin_batched  lambda_min of a symmetric block      (approx_eig_qr!; beyond the LDS kernels)
@@ -1473,6 +1474,84 @@ __global__ __launch_bounds__(NT) void trsm_batched(const TrsmDesc<T>* __restrict
       *bp = *bp - s;
     }
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// trsm_blk_update: the update of the blocked solve chain across workgroups (TrsmPlan::launch,
+// beyond the on-chip panel of trsm_batched).  The chain solves super-blocks of KB rows (a
+// multiple of NB) with trsm_batched on the sub-triangle at k0; this kernel then updates the rows
+// not yet solved with the kb = min(KB, n - k0) rows just solved,
+//   B[rest, :] -= L[rest, k0:k0+kb] X[k0:k0+kb, :]      (rest: below the super-block)
+//   TRANS:  B[rest, :] -= L[k0:k0+kb, rest]^T X[k0:k0+kb, :]   (rest: above it)
+// grid (row tiles x right-hand-side tiles, matrices), TR x TC elements per workgroup held in
+// registers; the L tile and the solved rows pass through LDS NB rows at a time.  Per element the
+// NB-row sub-blocks apply in trsm_batched's order (ascending; TRANS descending from the ragged
+// one), each as s = 0; s += l x for ascending q; b -= s: multi-word results are bitwise those of
+// the on-chip kernel.  A matrix with n <= k0 leaves the launch at once (batches mix sizes).
+// STORE_T as for trsm_batched; a unit diagonal plays no part here (off-diagonal entries only).
+// ------------------------------------------------------------------------------------------
+template <class T, bool TRANS, bool STORE_T, int NB, int TR, int TC, int NT>
+__global__ __launch_bounds__(NT) void trsm_blk_update(const TrsmDesc<T>* __restrict__ descs, int k0,
+                                                       int KB, int ntr) {
+  static_assert((TR * TC) % NT == 0 && NT % TR == 0, "whole elements per thread, one row each");
+  constexpr int EPT = TR * TC / NT;
+  const TrsmDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, tid = threadIdx.x;
+  if (n <= k0) return;
+  const int kb = min(KB, n - k0);
+  const int r0 = TRANS ? 0 : k0 + kb, nr = TRANS ? k0 : n - k0 - kb;
+  const int i0 = (blockIdx.x % ntr) * TR, c0 = (blockIdx.x / ntr) * TC;
+  if (i0 >= nr || c0 >= d.nrhs) return;
+  const int ti = min(TR, nr - i0), tc = min(TC, d.nrhs - c0);
+  const T* L = d.L;
+  const size_t ldl = d.ldl, ldb = d.ldb;
+  T* B = d.B + (size_t)c0 * ldb;
+  __shared__ T Ls[NB * TR];  // Ls[q * TR + i] = op(L)(r0 + i0 + i, j0 + q)
+  __shared__ T Xs[NB * TC];  // Xs[q * TC + c] = X(j0 + q, c0 + c)
+  // thread tid holds row tid % TR of columns tid / TR + k NT / TR (static indices: registers)
+  const int i = tid % TR, cf = tid / TR;
+  T b[EPT];
+#pragma unroll
+  for (int k = 0; k < EPT; ++k) {
+    const int c = cf + k * (NT / TR);
+    b[k] = T(0.0);
+    if (i < ti && c < tc) b[k] = B[(r0 + i0 + i) + (size_t)c * ldb];
+  }
+  // op(L)(row, col) sits at L[row + col ldl], or at L[col + row ldl] when exactly one of TRANS
+  // and STORE_T holds: the staging loads run along whichever index is contiguous
+  constexpr bool RM = TRANS != STORE_T;
+  const int nsb = (kb + NB - 1) / NB;
+  for (int sbi = 0; sbi < nsb; ++sbi) {
+    const int j0 = k0 + (TRANS ? nsb - 1 - sbi : sbi) * NB;
+    const int nb = min(NB, k0 + kb - j0);
+    for (int e = tid; e < NB * TR; e += NT) {
+      const int li = RM ? e / NB : e % TR, q = RM ? e % NB : e / TR;
+      if (li < ti && q < nb) {
+        const size_t row = r0 + i0 + li, col = j0 + q;
+        Ls[q * TR + li] = RM ? L[col + row * ldl] : L[row + col * ldl];
+      }
+    }
+    for (int e = tid; e < NB * TC; e += NT) {
+      const int q = e % NB, c = e / NB;
+      if (q < nb && c < tc) Xs[q * TC + c] = B[(j0 + q) + (size_t)c * ldb];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+      const int c = cf + k * (NT / TR);
+      if (i < ti && c < tc) {
+        T s = T(0.0);
+        for (int q = 0; q < nb; ++q) s += Ls[q * TR + i] * Xs[q * TC + c];
+        b[k] = b[k] - s;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < EPT; ++k) {
+    const int c = cf + k * (NT / TR);
+    if (i < ti && c < tc) B[(r0 + i0 + i) + (size_t)c * ldb] = b[k];
   }
 }
 

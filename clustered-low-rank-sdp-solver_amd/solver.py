@@ -383,6 +383,63 @@ def getrf(blocks, precision_words: int = 1, device: int = 0, raw_limbs: bool = F
     return LU, perms, info[:len(mats)].copy()
 
 
+def trsm(blocks, rhs, mode: int, trans: bool, precision_words: int = 1, device: int = 0,
+         raw_limbs: bool = False):
+    """Triangular solves ``op(T_b) X_b = B_b`` of each block at fp64 / double-double / quad-double
+    (clrsdp_trsm: approx_solve_tril! / approx_solve_triu!, as the solver's TrsmPlan runs them).
+    ``mode`` 0: the block holds a lower triangular L (potrf's); 1: the unit lower L of getrf's
+    factors; 2: their U, read transposed.  ``trans`` False solves L x = b (mode 2: U^T x = b),
+    True solves L^T x = b (mode 2: U x = b).  Blocks and right-hand sides (n x nrhs, or vectors of
+    length n) are float arrays, object arrays of mpmath numbers (split exactly into limbs) or raw
+    limbs of shape (words, n, n) / (words, n, nrhs).  Returns the solutions, one array per block
+    (floats at words 1, else the exact limb sums as mpmath numbers; with ``raw_limbs`` float
+    arrays of shape (words, n, nrhs))."""
+    w = int(precision_words)
+
+    def planes_of(a, vec_ok):
+        a = np.asarray(a)
+        if a.dtype != object and a.ndim == 3:      # raw limbs
+            if a.shape[0] != w:
+                raise ValueError("raw limbs need shape (words, rows, columns)")
+            return a.shape[1:], np.stack([a[q].reshape(-1, order="F") for q in range(w)]).astype(np.float64)
+        if vec_ok and a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2:
+            raise ValueError("blocks and right-hand sides must be matrices")
+        return a.shape, np.asarray(to_planes(a.reshape(-1, order="F"), w), dtype=np.float64).reshape(w, -1)
+
+    if len(blocks) != len(rhs):
+        raise ValueError("one right-hand side per block")
+    As, Bs, n, nr = [], [], [], []
+    for a, b in zip(blocks, rhs):
+        sa, pa = planes_of(a, False)
+        sb, pb = planes_of(b, True)
+        if sa[0] != sa[1]:
+            raise ValueError("blocks must be square")
+        if sb[0] != sa[0]:
+            raise ValueError("right-hand sides need as many rows as their block")
+        As.append(pa); Bs.append(pb); n.append(sa[0]); nr.append(sb[1])
+    n = np.array(n, dtype=np.int64)
+    nr = np.array(nr, dtype=np.int64)
+    A = np.ascontiguousarray(np.concatenate(As, axis=1)) if As else np.zeros((w, 0))
+    B = np.ascontiguousarray(np.concatenate(Bs, axis=1)) if Bs else np.zeros((w, 0))
+    _lib.check(_lib.lib().clrsdp_trsm(device, w, int(mode), 1 if trans else 0, len(As),
+                                      n.ctypes.data_as(_lib.P_i64), nr.ctypes.data_as(_lib.P_i64),
+                                      _ptr(A), _ptr(B)))
+    off = np.concatenate([[0], np.cumsum(n * nr)])
+    out = []
+    for b in range(len(As)):
+        seg = B[:, off[b]:off[b + 1]]
+        if raw_limbs:
+            out.append(seg.reshape((w, nr[b], n[b])).transpose(0, 2, 1).copy())
+        elif w == 1:
+            out.append(seg[0].reshape((n[b], nr[b]), order="F").copy())
+        else:
+            vals = from_planes(np.ascontiguousarray(seg).reshape(-1), int(n[b] * nr[b]), w)
+            out.append(np.asarray(vals, dtype=object).reshape((n[b], nr[b]), order="F"))
+    return out
+
+
 def initial_point(bi: BlockInfo, omega_p, omega_d):
     """x = 0, X = omega_p I, y = 0, Y = omega_d I (MPMP.jl:660-686)."""
     x = np.zeros(sum(bi.dim_S))

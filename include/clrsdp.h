@@ -339,6 +339,19 @@ int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int6
 int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                      double* A, int32_t* perm, int32_t* info);
 
+/* Triangular solves of each block in place on B_b (n[b] x nrhs[b]), as the solver runs them
+ * (approx_solve_tril! / approx_solve_triu!, MPMP.jl:1457-1460, 1751-1773): trsm_batched (the
+ * one-wave vector kernels for multi-word mode 0 blocks of n <= 128) wherever its on-chip panel
+ * fits, the blocked chain across workgroups beyond.  mode 0: A_b holds a lower triangular L
+ * (potrf's; the strict upper triangle is not read); mode 1: the unit lower L of clrsdp_getrf's
+ * factors (only the strict lower triangle is read); mode 2: their U, read transposed.  trans = 0
+ * solves L x = b (mode 2: U^T x = b), trans != 0 solves L^T x = b (mode 2: U x = b).  A: nblocks
+ * blocks of sizes n[] concatenated column-major as `words` planes; B likewise, block b with
+ * leading dimension n[b].  1 <= n[b], nrhs[b] <= 4096. */
+int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans,
+                    int64_t nblocks, const int64_t* n, const int64_t* nrhs,
+                    const double* A, double* B);
+
 #ifdef __cplusplus
 }
 #endif
