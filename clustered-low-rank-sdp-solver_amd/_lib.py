@@ -39,7 +39,7 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_comm_unique_id", "clrsdp_comm_init", "clrsdp_save_state",
            "clrsdp_restore_state", "clrsdp_step_length", "clrsdp_set_factorization",
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
-           "clrsdp_getrf", "clrsdp_trsm"]
+           "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf"]
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -128,6 +128,7 @@ def lib():
     L.clrsdp_comm_info.argtypes = [C.c_void_p, P_i32, P_i32]
     L.clrsdp_eigmin.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_f64]
     L.clrsdp_getrf.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32, P_i32]
+    L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]
     L.clrsdp_trsm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_i64,
                               P_f64, P_f64]
     L.clrsdp_step_length.argtypes = [C.c_int32, C.c_int64, P_i64, P_f64, P_f64, C.c_double, P_f64,

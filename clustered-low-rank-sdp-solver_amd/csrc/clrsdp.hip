@@ -777,8 +777,57 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   static constexpr int BLK_NB = 16;
   BlkPotrfDesc<T>* bd = nullptr;
   bool blk = false;
-  void finalize() {
+  // potrf_batched: 256 threads, double-double 1024 (see potrf())
+  static constexpr int PB_NT = std::is_same<T, mw::dd>::value ? 1024 : 256;
+  static size_t pb_lds_dyn(int n) { return sizeof(T) * ((size_t)NB * NB + (size_t)NB * n); }
+  // whether potrf() factors matrices up to n by potrf_batched (the rest: chol_lookahead or the
+  // potrf_blk_* chain, neither with a size bound)
+  static bool takes_potrf_batched(int n) {
+    if (std::is_same<T, double>::value) return true;
+    if (std::is_same<T, mw::dd>::value) return n > LA_NMAX && env_off("CLRSDP_POTRF_BLK");
+    return n > LA_NMAX;
+  }
+  // static LDS of potrf_batched (rdg[], fail), from the code object (asked once per word type)
+  static size_t pb_lds_static() {
+    static const size_t bytes = [] {
+      hipFuncAttributes fa;
+      HIPCHK(hipFuncGetAttributes(&fa, (const void*)potrf_batched<T, NB, PB_NT>));
+      return (size_t)fa.sharedSizeBytes;
+    }();
+    return bytes;
+  }
+  // the largest n whose 16-column panel (dynamic) and static LDS fit one CU
+  static int pb_nmax() {
+    const size_t st = pb_lds_static();
+    return (int)((LDS_MAX - st - sizeof(T) * NB * NB) / (sizeof(T) * NB));
+  }
+  // Past potrf_batched's panel the runtime would refuse the launch: the message of the refusal
+  // (CLRSDP_E_ARG) for matrices up to nmax, empty where potrf() can run
+  static std::string potrf_refusal(int nmax) {
+    if (!takes_potrf_batched(nmax) || pb_lds_dyn(nmax) + pb_lds_static() <= LDS_MAX) return std::string();
+    const char* w = std::is_same<T, double>::value ? "fp64" : std::is_same<T, mw::dd>::value ? "double-double" : "quad-double";
+    return std::string("Cholesky factorization: a matrix of n = ") + std::to_string(nmax) +
+           " is too large for the on-chip panel of potrf_batched (" + w + ": n <= " + std::to_string(pb_nmax()) + ")";
+  }
+  static void check_potrf(int nmax) {
+    const std::string r = potrf_refusal(nmax);
+    if (!r.empty()) throw ClrsdpError{CLRSDP_E_ARG, r};
+  }
+  std::string refused;  // potrf() throws this (before any launch) instead of launching
+  // What the plan is for, which decides how finalize() treats potrf_batched's size bound:
+  //   FACTOR           potrf() runs: a plan past the bound is refused by finalize();
+  //   FACTOR_DEFERRED  the solver's plans: a plan past the bound is built all the same and
+  //                    refused when potrf() is called, since a handle of that size still runs
+  //                    every stage before FACTOR, and FACTOR itself with CLRSDP_FACT_LU_SQ
+  //                    (pivoted LU has no size bound);
+  //   EIG_ONLY         only eigmin() runs: no such bound
+  enum class Use { FACTOR, FACTOR_DEFERRED, EIG_ONLY };
+  void finalize(Use use = Use::FACTOR) {
     if (h.empty()) return;
+    if (use != Use::EIG_ONLY) {
+      refused = potrf_refusal(nmax);
+      if (!refused.empty() && use == Use::FACTOR) throw ClrsdpError{CLRSDP_E_ARG, refused};
+    }
     d = own(h);
     if constexpr (std::is_same<T, mw::dd>::value) {
       blk = nmax > 64 && !env_off("CLRSDP_POTRF_BLK");
@@ -794,6 +843,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   }
   void potrf(hipStream_t s, int* info) const {
     if (h.empty()) return;
+    if (!refused.empty()) throw ClrsdpError{CLRSDP_E_ARG, refused};
     if constexpr (std::is_same<T, mw::dd>::value) {
       if (blk) {
         constexpr int NB = BLK_NB, DT = NB / 16;
@@ -1011,7 +1061,8 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
       if (nmax <= 32) go<32>(s, nb, info);
       else if (nmax <= 64) go<64>(s, nb, info);
       else if (nmax <= 128) go<128>(s, nb, info);
-      else go<256>(s, nb, info);
+      else if (nmax <= 256) go<256>(s, nb, info);
+      else throw ClrsdpError{CLRSDP_E_ARG, "on-chip fp64 factorisation with inverse (chol_inv_tiles): n <= 256 only"};
     } else {
       // chol_lookahead with L^-1 (quad-double: the square-root-free LDL form).  Blocks n <= 32
       // on 4 waves -- one per SIMD, the chain alone on its SIMD -- instead of 16 (C5's X/Y
@@ -1025,7 +1076,8 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
   }
   template <int NP>
   void go(hipStream_t s, unsigned nb, int* info) const {
-    static_assert(sizeof(double) * CholTiles<NP>::END + 16 <= LDS_MAX, "chol_inv_tiles: LDS");
+    static_assert(sizeof(double) * CholTiles<NP>::END + sizeof(int) * CholTiles<NP>::NFLAGS <= LDS_MAX,
+                  "chol_inv_tiles: LDS");
     const size_t lds = chol_inv_tiles_lds<NP>();
     // raised wave priority: the factorisation's chains keep their issue slots against the side
     // streams' GEMM waves on the same SIMDs
@@ -1630,8 +1682,8 @@ struct Solver final : HandleBase {
           e_Xs.add(tB + b.off, b.n, b.n);
           e_Ys.add(tC + b.off, b.n, b.n);
         }
-        e_Xs.finalize();
-        e_Ys.finalize();
+        e_Xs.finalize(MatPlan<T>::Use::EIG_ONLY);
+        e_Ys.finalize(MatPlan<T>::Use::EIG_ONLY);
         // CLRSDP_XY_OVERLAP=1 (round 6): with at most 32 local blocks the
         // X step length (its congruence and eigen launch) runs on the side stream as soon as the
         // corrector's dX exists, beside dY and the Y step length.  Measured, not the default
@@ -1868,10 +1920,11 @@ struct Solver final : HandleBase {
                            &p_wA_Ps, &p_wA_dXs, &p_xir})
       g->finalize();
     for (CholInvPlan<T>* c : {&ci_XY, &ci_S, &ci_S22, &ci_Q}) c->finalize();
-    e_XY.finalize();
+    e_XY.finalize(MatPlan<T>::Use::EIG_ONLY);
     for (TrsmPlan<T>* t : {&t_Linv, &t_W, &t_t, &t_Q, &t_sX1, &t_sX2, &t_sY1, &t_sY2, &t_dx, &t_Sinv, &t_Qinv})
       t->finalize();
-    for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q, &e_X, &e_Y}) f->finalize();
+    for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q}) f->finalize(MatPlan<T>::Use::FACTOR_DEFERRED);
+    for (MatPlan<T>* f : {&e_X, &e_Y}) f->finalize(MatPlan<T>::Use::EIG_ONLY);
   }
 
   // ---- double-double Schur products on the int8 matrix cores (Ozaki scheme, oz_split / oz_gemm in
@@ -3736,7 +3789,7 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
   HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
   MatPlan<T> eg;
   for (int64_t b = 0; b < nblk; ++b) eg.add(A + off[b], (int)n[b], (int)n[b]);
-  eg.finalize();
+  eg.finalize(MatPlan<T>::Use::EIG_ONLY);
   hipStream_t s = nullptr;
   HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
@@ -3780,6 +3833,54 @@ void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t
   HIPCHK(hipMemcpy(h.data(), A, (size_t)tot * sizeof(T), hipMemcpyDeviceToHost));
   static_assert(sizeof(int) == sizeof(int32_t), "perm and info are 32-bit");
   HIPCHK(hipMemcpy(perm, dperm, (size_t)np * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  for (int64_t e = 0; e < tot; ++e)
+    for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
+}
+
+// Cholesky factor of each block at the word type T, as the solver runs it: in place through
+// MatPlan::potrf (inverse = 0), or L^-1 through CholInvPlan into a buffer of its own that holds
+// NaN bytes before the launch, so every entry that comes back was written by the kernel
+// (inverse = 1); planes in and out
+template <class T>
+void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double* Ap, int32_t* info) {
+  constexpr int W = Num<T>::W;
+  std::vector<int64_t> off(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) off[b + 1] = off[b] + n[b] * n[b];
+  DeviceGuard dg(device);
+  // potrf_batched's size bound (E_ARG) before any buffer is allocated or copied; fac.finalize()
+  // below makes the same comparison again, on the cached figure
+  if (!inverse) MatPlan<T>::check_potrf((int)*std::max_element(n, n + nblk));
+  const int64_t tot = off[nblk];
+  std::vector<double> h((size_t)tot * W);
+  for (int64_t e = 0; e < tot; ++e)
+    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
+  DevBuf mem;
+  T* A = mem.alloc<T>(tot);
+  T* X = inverse ? mem.alloc<T>(tot) : nullptr;
+  int* dinfo = mem.alloc<int>(nblk);
+  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
+  MatPlan<T> fac;
+  CholInvPlan<T> ci;
+  for (int64_t b = 0; b < nblk; ++b) {
+    if (inverse) ci.add(A + off[b], (int)n[b], (int)n[b], X + off[b], (int)n[b]);
+    else fac.add(A + off[b], (int)n[b], (int)n[b]);
+  }
+  fac.finalize();
+  ci.finalize();
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  if (inverse) {
+    HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)tot * sizeof(T), s));
+    ci.launch(s, dinfo);
+  } else {
+    fac.potrf(s, dinfo);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(h.data(), inverse ? X : A, (size_t)tot * sizeof(T), hipMemcpyDeviceToHost));
+  static_assert(sizeof(int) == sizeof(int32_t), "info is 32-bit");
   HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
   for (int64_t e = 0; e < tot; ++e)
     for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
@@ -3867,7 +3968,7 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
     }
     eg.add(t2 + o, nb, nb);
   }
-  ci.finalize(); g1.finalize(); g2.finalize(); fac.finalize(); eg.finalize();
+  ci.finalize(); g1.finalize(); g2.finalize(); fac.finalize(); eg.finalize(MatPlan<double>::Use::EIG_ONLY);
   s1.finalize(); s2.finalize();
   PlanBase bd_owner;
   BlkDesc* d_big = big.empty() ? nullptr : bd_owner.own(big);
@@ -4119,6 +4220,34 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
     if (words == 1) getrf_words<double>(device, nblocks, n, A, perm, info);
     else if (words == 2) getrf_words<mw::dd>(device, nblocks, n, A, perm, info);
     else getrf_words<mw::qd>(device, nblocks, n, A, perm, info);
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nblocks,
+                     const int64_t* n, double* A, int32_t* info) {
+  if (nblocks <= 0 || !n || !A || !info) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
+  if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  if (inverse != 0 && inverse != 1) { g_last_error = "inverse must be 0 or 1"; return CLRSDP_E_ARG; }
+  const int64_t inv_max = words == 1 ? 256 : 64;  // chol_inv_tiles / chol_lookahead with L^-1
+  for (int64_t b = 0; b < nblocks; ++b) {
+    if (n[b] <= 0 || n[b] > 4096) { g_last_error = "block size out of range"; return CLRSDP_E_ARG; }
+    if (inverse && n[b] > inv_max) {
+      g_last_error = words == 1 ? "L^-1 on chip (chol_inv_tiles): n <= 256 only"
+                                : "L^-1 on chip (chol_lookahead with the inverse): n <= 64 only";
+      return CLRSDP_E_ARG;
+    }
+  }
+  try {
+    if (words == 1) potrf_words<double>(device, inverse, nblocks, n, A, info);
+    else if (words == 2) potrf_words<mw::dd>(device, inverse, nblocks, n, A, info);
+    else potrf_words<mw::qd>(device, inverse, nblocks, n, A, info);
     return CLRSDP_OK;
   } catch (const ClrsdpError& e) {
     g_last_error = e.msg;

@@ -363,7 +363,8 @@ __device__ __forceinline__ void potrf_blk_diag(const BlkPotrfDesc<T>& b, int k0,
   const MatDesc<T> dk{b.A + k0 + (size_t)k0 * b.lda, nb, b.lda};
   const MatDesc<T> oi{b.Linv, nb, NB};
   const int f = chol_lookahead_body<T, true, LDL, NB, 3>(dk, oi, dk, opts);
-  if (threadIdx.x == 0 && info && f) info[m] = k0 + f;
+  // (the first failure stays: the panels after it run on what it left and fail again)
+  if (threadIdx.x == 0 && info && f && info[m] == 0) info[m] = k0 + f;
 }
 
 template <class T, bool LDL, int NB>
@@ -2829,6 +2830,9 @@ struct CholTiles {
   static constexpr int XLD = NP + 16;   // X row block: 16 x XLD row-major
   static constexpr int DT = 0, PN = DT + NT * 16 * LDD, XR = PN + NT * 256, DI = XR + 16 * XLD,
                        END = DI + 512;  // doubles; the int flags follow
+  // flag[0], flag[3]: the failure slots by tile parity; flag[1]: look-ahead panels ready;
+  // flag[2]: worker arrivals (chol_inv_tiles)
+  static constexpr int NFLAGS = 4;
   static __device__ __forceinline__ void tile(int t, int& i, int& j) {  // row-major lower
     i = 1;
     while (i * (i + 1) / 2 <= t) ++i;
@@ -2836,7 +2840,7 @@ struct CholTiles {
   }
 };
 template <int NP>
-size_t chol_inv_tiles_lds() { return sizeof(double) * CholTiles<NP>::END + 16; }
+size_t chol_inv_tiles_lds() { return sizeof(double) * CholTiles<NP>::END + sizeof(int) * CholTiles<NP>::NFLAGS; }
 
 template <int NP>
 __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDesc<double>* __restrict__ in,
@@ -2857,6 +2861,14 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
   double* Xr = reinterpret_cast<double*>(smem_raw) + CT::XR;  // X row block k
   double* Di = reinterpret_cast<double*>(smem_raw) + CT::DI;  // Linv_kk by parity, col-major
   int* flag = reinterpret_cast<int*>(reinterpret_cast<double*>(smem_raw) + CT::END);
+  // The failure of diagonal tile t is published in FAIL(t), a slot chosen by the tile's parity.
+  // The chain wave factors D_{k+1} during panel k, and every wave decides to leave at the top of
+  // panel k from FAIL(k): written during panel k - 1 (D_0: the prologue), so before the barrier
+  // that ended it, and all waves read the same value.  (One slot for every tile let a worker that
+  // read it late in panel k leave while the others, having read 0, spun on its flag + 2 arrival.)
+  // At most one slot is ever set: every wave leaves at the top of the panel after the failure.
+  static_assert(CT::NFLAGS == 4, "flag[0..3] are used below");
+  auto FAIL = [&](int t) { return flag + 3 * (t & 1); };
 #ifdef CLRSDP_CHOL_TRACE
   int tr_i = 0;
 #endif
@@ -2911,9 +2923,10 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
   if (wk < 0) {
     // ======================= the chain wave: the diagonal tiles, one panel ahead
     if (lane == 0) {  // (before D_0's factorisation, which may set flag[0])
-      flag[0] = 0;  // first failing pivot + 1
+      flag[0] = 0;  // first failing pivot + 1 of an even diagonal tile (FAIL above)
       flag[1] = 0;  // panels whose L_{k+1,k} is in the panel buffer
       flag[2] = 0;  // worker arrivals at the (b) -> (c) barrier
+      flag[3] = 0;  // first failing pivot + 1 of an odd diagonal tile
     }
     prologue_load();
     chol_diag16_pipe(Dt, [](int i, int j) { return j * LDD + i; },
@@ -2926,7 +2939,7 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
     lds_barrier();
     CT_TRACE();
     for (int k = 0; k < nt; ++k) {
-      if (*flag) break;
+      if (*FAIL(k)) break;
       if (k + 1 < nt) {
         // D_{k+1} -= L L^T (L = L_{k+1,k}) and its factorisation
         // (the flags order LDS data only: relaxed LDS atomics and compiler fences, so neither
@@ -2949,7 +2962,7 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
         for (int r = 0; r < 4; ++r) D[lr * LDD + lk + 4 * r] = acc[r];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         chol_diag16_pipe(D, [](int i, int j) { return j * LDD + i; }, 16 * (k + 1),
-                         Di + 256 * ((k + 1) & 1), flag, lane);
+                         Di + 256 * ((k + 1) & 1), FAIL(k + 1), lane);
         CT_TRACE();
       }
       lds_barrier();
@@ -2985,7 +2998,7 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
     lds_barrier();  // (the chain wave's first diagonal factor)
     CT_TRACE();
     for (int k = 0; k < nt; ++k) {
-      if (*flag) break;
+      if (*FAIL(k)) break;
       // an opaque zero per panel: the per-slot LDS and store addresses below are formed where
       // they are used, not hoisted out of the loop (NP = 256: dozens of loop-invariant
       // addresses kept live across the panels spilled to scratch)
@@ -3101,7 +3114,7 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
       CT_TRACE();
     }
   }
-  if (tid == 0 && info) info[blockIdx.x] = *flag;
+  if (tid == 0 && info) info[blockIdx.x] = flag[0] ? flag[0] : flag[3];
   CT_TRACE();
 }
 #undef CT_TRACE

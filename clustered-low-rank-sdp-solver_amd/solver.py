@@ -383,6 +383,54 @@ def getrf(blocks, precision_words: int = 1, device: int = 0, raw_limbs: bool = F
     return LU, perms, info[:len(mats)].copy()
 
 
+def potrf(blocks, inverse: bool = False, precision_words: int = 1, device: int = 0,
+          raw_limbs: bool = False):
+    """Cholesky factor ``A = L L^T`` of each symmetric positive definite block at fp64 /
+    double-double / quad-double (clrsdp_potrf: cho!, as the solver's potrf plan runs it), or with
+    ``inverse`` its inverse ``L^-1`` (the on-chip factorisation with the inverse: n <= 256 at
+    fp64, n <= 64 at multi-word).  Blocks are float arrays, object arrays of mpmath numbers (split
+    exactly into limbs) or raw limbs of shape (words, n, n); only their lower triangles are used.
+    Returns ``(L, info)``: per block the lower triangle of the result (``np.tril``: floats at
+    words 1, else the exact limb sums as mpmath numbers) and ``info`` = 0 or the 1-based column of
+    the first pivot that is not positive (fp64 with ``inverse``: the first column of its
+    16-column tile); a failed block's contents are unspecified.  With ``raw_limbs`` the whole
+    blocks come back as the device left them, one float array of shape (words, n, n) each."""
+    w = int(precision_words)
+    planes, n = [], []
+    for a in blocks:
+        a = np.asarray(a)
+        if a.dtype != object and a.ndim == 3:      # raw limbs
+            if a.shape[0] != w:
+                raise ValueError("raw limbs need shape (words, n, n)")
+            if a.shape[1] != a.shape[2]:
+                raise ValueError("blocks must be square")
+            pl = np.stack([a[q].reshape(-1, order="F") for q in range(w)]).astype(np.float64)
+        else:
+            if a.ndim != 2 or a.shape[0] != a.shape[1]:
+                raise ValueError("blocks must be square")
+            pl = np.asarray(to_planes(a.reshape(-1, order="F"), w), dtype=np.float64).reshape(w, -1)
+        planes.append(pl)
+        n.append(a.shape[-1])
+    n = np.array(n, dtype=np.int64)
+    A = np.ascontiguousarray(np.concatenate(planes, axis=1)) if planes else np.zeros((w, 0))
+    info = np.zeros(max(len(planes), 1), dtype=np.int32)
+    _lib.check(_lib.lib().clrsdp_potrf(device, w, 1 if inverse else 0, len(planes),
+                                       n.ctypes.data_as(_lib.P_i64), _ptr(A),
+                                       info.ctypes.data_as(_lib.P_i32)))
+    off = np.concatenate([[0], np.cumsum(n * n)])
+    out = []
+    for b in range(len(planes)):
+        seg = A[:, off[b]:off[b + 1]]
+        if raw_limbs:
+            out.append(seg.reshape((w, n[b], n[b])).transpose(0, 2, 1).copy())
+        elif w == 1:
+            out.append(np.tril(seg[0].reshape((n[b], n[b]), order="F")))
+        else:
+            vals = from_planes(np.ascontiguousarray(seg).reshape(-1), int(n[b] * n[b]), w)
+            out.append(np.tril(np.asarray(vals, dtype=object).reshape((n[b], n[b]), order="F")))
+    return out, info[:len(planes)].copy()
+
+
 def trsm(blocks, rhs, mode: int, trans: bool, precision_words: int = 1, device: int = 0,
          raw_limbs: bool = False):
     """Triangular solves ``op(T_b) X_b = B_b`` of each block at fp64 / double-double / quad-double

@@ -339,6 +339,30 @@ int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int6
 int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                      double* A, int32_t* perm, int32_t* info);
 
+/* Cholesky factorisation of each symmetric positive definite block, A_b = L_b L_b^T (cho!,
+ * MPMP.jl:1433-1442, 1499-1505, 1846), by the kernels the loop body runs.  A: nblocks blocks of
+ * sizes n[] (1 <= n[b] <= 4096) concatenated column-major as `words` planes (1, 2 or 4; hi limb
+ * first).  Only the lower triangle of a block is used: whatever stands above the diagonal on
+ * entry, NaN included, does not change the result.
+ *   inverse = 0: in place through the solver's potrf plan.  On return the lower triangle holds
+ *     L_b; the strict upper triangle is unspecified (potrf_batched leaves the input there, the
+ *     other kernels write zeros).  fp64: potrf_batched at every n; double-double: chol_lookahead
+ *     up to 64 and the potrf_blk_* chain across workgroups beyond (CLRSDP_POTRF_BLK=0:
+ *     chol_lookahead up to 128, potrf_batched beyond); quad-double: chol_lookahead (LDL form) up
+ *     to 64, potrf_batched beyond.  potrf_batched keeps a 16-column panel of the matrix on chip:
+ *     past the n at which it fits (fp64 1262, quad-double 302, double-double 622) the call is
+ *     CLRSDP_E_ARG, as the loop body's Cholesky of such a block is (clrsdp_iterate,
+ *     clrsdp_run_stage; with CLRSDP_FACT_LU_SQ the body factors it by pivoted LU instead).
+ *   inverse = 1: A receives L_b^-1 (chol_inv_tiles at fp64, n[b] <= 256; chol_lookahead with
+ *     the inverse at double-double and quad-double, n[b] <= 64; larger: CLRSDP_E_ARG).  The
+ *     lower triangle holds L_b^-1 and the strict upper triangle exact zeros, every entry written
+ *     by the kernel.
+ * info: nblocks values, 0 or the 1-based column of the first pivot that is not positive (NaN
+ * included); at fp64 with inverse = 1 the first column of the 16-column diagonal tile that holds
+ * it.  After a failure that block's contents are unspecified; the other blocks are complete. */
+int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nblocks,
+                     const int64_t* n, double* A, int32_t* info);
+
 /* Triangular solves of each block in place on B_b (n[b] x nrhs[b]), as the solver runs them
  * (approx_solve_tril! / approx_solve_triu!, MPMP.jl:1457-1460, 1751-1773): trsm_batched (the
  * one-wave vector kernels for multi-word mode 0 blocks of n <= 128) wherever its on-chip panel
