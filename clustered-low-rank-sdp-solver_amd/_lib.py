@@ -39,10 +39,19 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_comm_unique_id", "clrsdp_comm_init", "clrsdp_save_state",
            "clrsdp_restore_state", "clrsdp_step_length", "clrsdp_set_factorization",
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
-           "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf"]
+           "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain"]
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
+# clrsdp_gemm forms, the kernel codes of its *path, clrsdp_gemm_chain forms (include/clrsdp.h)
+GEMM_PLAIN, GEMM_SYM, GEMM_UPPER, GEMM_SCALED, GEMM_MIXED = range(5)
+(PATH_GEMV_N_F64, PATH_GEMV_T_F64, PATH_GEMV_N_MW, PATH_GEMV_T_QD, PATH_GEMV_T_DD, PATH_UNI64,
+ PATH_UNI32, PATH_LDS, PATH_DYN, PATH_VALU_KS) = range(1, 11)
+PATH_NAMES = {1: "gemv_batched fp64 N", 2: "gemv_batched fp64 T", 3: "gemv_batched multi-word N",
+              4: "gemv_batched qd T (deep)", 5: "gemv_batched dd T (16-lane)",
+              6: "gemm_f64_uni 64", 7: "gemm_f64_uni 32", 8: "gemm_f64_lds", 9: "gemm_f64_dyn",
+              10: "gemm_valu_ks"}
+CHAIN, CHAIN_SYM, CHAIN_TRACE = range(3)
 
 P_i64 = C.POINTER(C.c_int64)
 P_i32 = C.POINTER(C.c_int32)
@@ -79,6 +88,14 @@ class IterStats(C.Structure):
                 ("inner_ms", C.c_double * NUM_INNER), ("gap_w", C.c_double * 4),
                 ("P_err_w", C.c_double * 4), ("p_err_w", C.c_double * 4),
                 ("d_err_w", C.c_double * 4)]
+
+
+class GemmProblem(C.Structure):
+    _fields_ = [("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64), ("lda", C.c_int64),
+                ("ldb", C.c_int64), ("ldc", C.c_int64), ("ldcin", C.c_int64), ("offa", C.c_int64),
+                ("offb", C.c_int64), ("offc", C.c_int64), ("offcin", C.c_int64), ("offs", C.c_int64),
+                ("transa", C.c_int32), ("transb", C.c_int32), ("diag", C.c_int32),
+                ("reserved", C.c_int32), ("alpha", C.c_double), ("beta", C.c_double)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p)
@@ -131,6 +148,12 @@ def lib():
     L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]
     L.clrsdp_trsm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_i64,
                               P_f64, P_f64]
+    L.clrsdp_gemm.argtypes = [C.c_int32] * 5 + [C.c_double, C.c_double, P_f64, C.c_double, C.c_int64,
+                              C.POINTER(GemmProblem), P_f64, C.c_int64, P_f64, C.c_int64, P_f64,
+                              C.c_int64, P_f64, C.c_int64, P_f64, P_f64, C.c_int64, P_i32]
+    L.clrsdp_gemm_chain.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                    C.c_double, C.c_double] + [P_f64] * 11 + [C.c_double, C.c_double,
+                                                                             P_f64]
     L.clrsdp_step_length.argtypes = [C.c_int32, C.c_int64, P_i64, P_f64, P_f64, C.c_double, P_f64,
                                      P_f64]
     for name in EXPORTS:

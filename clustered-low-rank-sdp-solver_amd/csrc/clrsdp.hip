@@ -40,11 +40,15 @@ struct ClrsdpError {
   std::string msg;
 };
 
+// (the runtime also keeps a failed call's code for the thread's next hipGetLastError(); it is
+// reported here, so it is cleared here: the launch check of a later, good call must not find it)
 #define HIPCHK(x)                                                                   \
   do {                                                                              \
     hipError_t e_ = (x);                                                            \
-    if (e_ != hipSuccess)                                                           \
+    if (e_ != hipSuccess) {                                                         \
+      (void)hipGetLastError();                                                      \
       throw ClrsdpError{CLRSDP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)}; \
+    }                                                                               \
   } while (0)
 
 // zero-filled device allocation; the fill is complete on return (null stream, synchronised:
@@ -64,7 +68,10 @@ X* dmalloc(size_t n) {
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) {
+      prev = -1;
+      (void)hipGetLastError();
+    }
     if (prev != dev) HIPCHK(hipSetDevice(dev));
   }
   ~DeviceGuard() {
@@ -388,6 +395,21 @@ struct GemmPlan : PlanBase {
   void launch_uni_impl(hipStream_t s, double alpha, double beta, const double* ds, double dmult) const;
   void launch_uni(hipStream_t s, double alpha, double beta, const double* ds, double dmult) const {
     launch_uni_impl<T>(s, alpha, beta, ds, dmult);
+  }
+  // the kernel launch() takes after finalize() (CLRSDP_PATH_*, include/clrsdp.h; 0: empty plan),
+  // from the fields it branches on, in its order
+  int path() const {
+    if (h.empty()) return 0;
+    constexpr bool f64 = std::is_same<T, double>::value;
+    if (gemv) {
+      if (f64) return ta ? CLRSDP_PATH_GEMV_T_F64 : CLRSDP_PATH_GEMV_N_F64;
+      if (!ta) return CLRSDP_PATH_GEMV_N_MW;
+      return std::is_same<T, mw::dd>::value ? CLRSDP_PATH_GEMV_T_DD : CLRSDP_PATH_GEMV_T_QD;
+    }
+    if (!f64) return CLRSDP_PATH_VALU_KS;
+    if (uni) return uts == 32 ? CLRSDP_PATH_UNI32 : CLRSDP_PATH_UNI64;
+    if (sca) return CLRSDP_PATH_LDS;
+    return dyn ? CLRSDP_PATH_DYN : CLRSDP_PATH_LDS;
   }
   // C = alpha op(A) op(B) + beta Cin (+ dmult * *dscal on the diagonal of square problems)
   void launch(hipStream_t s, double alpha, double beta, const T* dscal = nullptr,
@@ -3925,6 +3947,211 @@ void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n,
     for (int q = 0; q < W; ++q) Bp[(size_t)q * totb + e] = hb[(size_t)e * W + q];
 }
 
+// planes of an arena of `cnt` numbers <-> the interleaved limbs of T (bit copies: a NaN keeps
+// its payload)
+template <class T>
+std::vector<double> interleave(const double* planes, int64_t cnt) {
+  constexpr int W = Num<T>::W;
+  std::vector<double> h((size_t)cnt * W);
+  for (int q = 0; q < W; ++q)
+    for (int64_t e = 0; e < cnt; ++e)
+      std::memcpy(&h[(size_t)e * W + q], &planes[(size_t)q * cnt + e], sizeof(double));
+  return h;
+}
+template <class T>
+T* upload_planes(DevBuf& mem, const double* planes, int64_t cnt) {
+  T* d = mem.alloc<T>((size_t)cnt);
+  const std::vector<double> h = interleave<T>(planes, cnt);
+  if (cnt) HIPCHK(hipMemcpy(d, h.data(), (size_t)cnt * sizeof(T), hipMemcpyHostToDevice));
+  return d;
+}
+template <class T>
+void download_planes(const T* d, double* planes, int64_t cnt) {
+  constexpr int W = Num<T>::W;
+  std::vector<double> h((size_t)cnt * W);
+  if (cnt) HIPCHK(hipMemcpy(h.data(), d, (size_t)cnt * sizeof(T), hipMemcpyDeviceToHost));
+  for (int q = 0; q < W; ++q)
+    for (int64_t e = 0; e < cnt; ++e)
+      std::memcpy(&planes[(size_t)q * cnt + e], &h[(size_t)e * W + q], sizeof(double));
+}
+
+// the arguments of clrsdp_gemm, checked by the caller (gemm_check)
+struct GemmCall {
+  int form, ta, tb;
+  double alpha, beta;
+  const double* dscal;
+  double dmult;
+  int64_t nprob;
+  const clrsdp_gemm_problem* pr;
+  const double *A, *B, *Cin, *sa, *sl;
+  double* C;
+  int64_t na, nb, nc, ncin, ns;
+};
+
+// One GemmPlan<T> from the records, built as build_plans() builds the solver's, launched once
+template <class T>
+int gemm_words(int device, const GemmCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  const T* A = upload_planes<T>(mem, c.A, c.na);
+  const T* B = upload_planes<T>(mem, c.B, c.nb);
+  T* C = upload_planes<T>(mem, c.C, c.nc);
+  const T* Cin = c.Cin ? upload_planes<T>(mem, c.Cin, c.ncin) : nullptr;
+  const T* sa = c.sa ? upload_planes<T>(mem, c.sa, c.ns) : nullptr;
+  const T* sl = c.sl ? upload_planes<T>(mem, c.sl, c.ns) : nullptr;
+  const T* ds = nullptr;
+  if (c.dscal) {
+    T* d1 = mem.alloc<T>(1);
+    const T v = T(*c.dscal);
+    HIPCHK(hipMemcpy(d1, &v, sizeof(T), hipMemcpyHostToDevice));
+    ds = d1;
+  }
+  GemmPlan<T> g;
+  g.ta = c.ta != 0;
+  g.tb = c.tb != 0;
+  g.sym = c.form == CLRSDP_GEMM_SYM;
+  g.upper = c.form == CLRSDP_GEMM_UPPER;
+  for (int64_t p = 0; p < c.nprob; ++p) {
+    const clrsdp_gemm_problem& r = c.pr[p];
+    const double be = c.form == CLRSDP_GEMM_MIXED ? r.beta : c.beta;
+    const bool inplace = !Cin || r.offcin < 0;
+    const T* ci = be == 0.0 && inplace ? nullptr : inplace ? C + r.offc : Cin + r.offcin;
+    const int ldci = (int)(inplace ? r.ldc : r.ldcin);
+    const int M = (int)r.M, N = (int)r.N, K = (int)r.K;
+    if (c.form == CLRSDP_GEMM_SCALED) {
+      g.add_scaled(A + r.offa, (int)r.lda, B + r.offb, (int)r.ldb, ci, ldci, C + r.offc, (int)r.ldc,
+                   M, N, K, sa + r.offs, sl + r.offs);
+    } else if (c.form == CLRSDP_GEMM_MIXED) {
+      g.add_op(r.transa != 0, r.transb != 0, r.alpha, r.beta, A + r.offa, (int)r.lda, B + r.offb,
+               (int)r.ldb, ci, ldci, C + r.offc, (int)r.ldc, M, N, K);
+      if (r.diag) {  // + *dscal on the diagonal, as XINV's R = mu_p I - X Y
+        g.h.back().flags |= 16;
+        g.h.back().sa = ds;
+      }
+    } else {
+      g.add(A + r.offa, (int)r.lda, B + r.offb, (int)r.ldb, ci, ldci, C + r.offc, (int)r.ldc, M, N, K);
+    }
+  }
+  g.finalize();
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  g.launch(s, c.alpha, c.beta, c.form == CLRSDP_GEMM_MIXED ? nullptr : ds, c.dmult);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
+  download_planes<T>(C, c.C, c.nc);
+  return g.path();
+}
+
+// the argument checks of clrsdp_gemm: an empty string, or what is wrong (no device call)
+std::string gemm_check(int words, const GemmCall& c) {
+  if (c.nprob <= 0 || c.nprob > 65536 || !c.pr || !c.A || !c.B || !c.C) return "null argument or no problems";
+  if (words != 1 && words != 2 && words != 4) return "words must be 1, 2 or 4";
+  if (c.form < CLRSDP_GEMM_PLAIN || c.form > CLRSDP_GEMM_MIXED) return "unknown form";
+  const bool sym = c.form == CLRSDP_GEMM_SYM, upper = c.form == CLRSDP_GEMM_UPPER,
+             sca = c.form == CLRSDP_GEMM_SCALED, mixed = c.form == CLRSDP_GEMM_MIXED;
+  if ((sym || sca || mixed || c.dscal) && words != 1)
+    return "SYM, SCALED, MIXED and the diagonal scalar are fp64 only";
+  if (upper && words == 1) return "UPPER is multi-word only";
+  if (sca && (c.ta || !c.tb)) return "scaled-A GEMM: fp64 A B^T only";
+  if (sca && (!c.sa || !c.sl)) return "scaled-A GEMM: sa and sl required";
+  if (sym && c.ta) return "symmetric GEMM epilogue: op(A) = A only";
+  if (sym && (c.beta != 0.0 || c.dscal)) return "symmetric GEMM epilogue: beta = 0 only";
+  if (c.na < 0 || c.nb < 0 || c.nc < 0 || (c.Cin && c.ncin < 0) || (sca && c.ns < 0)) return "negative arena length";
+  constexpr int64_t LDMAX = 1 << 24;
+  bool gemv = !mixed && !sca;
+  std::vector<std::pair<int64_t, int64_t>> cs;
+  // footprint of a column-major rows x cols matrix at `off` inside an arena of `len` numbers
+  auto inside = [](int64_t off, int64_t rows, int64_t cols, int64_t ld, int64_t len) {
+    return off >= 0 && off <= len && (cols - 1) * ld + rows <= len - off;
+  };
+  for (int64_t p = 0; p < c.nprob; ++p) {
+    const clrsdp_gemm_problem& r = c.pr[p];
+    if (r.M < 1 || r.M > 4096 || r.N < 1 || r.N > 4096) return "M and N must be 1 .. 4096";
+    if (r.K < 1 || r.K > 4096) return "K must be 1 .. 4096 (block without vectors)";
+    if ((sym || upper) && r.M != r.N) return "symmetric GEMM epilogue: square problems only";
+    const bool ta = mixed ? r.transa != 0 : c.ta != 0, tb = mixed ? r.transb != 0 : c.tb != 0;
+    const double be = mixed ? r.beta : c.beta;
+    const int64_t ar = ta ? r.K : r.M, ac = ta ? r.M : r.K, br = tb ? r.N : r.K, bc = tb ? r.K : r.N;
+    const bool separate = be != 0.0 && c.Cin && r.offcin >= 0;
+    if (r.lda < ar || r.ldb < br || r.ldc < r.M || (separate && r.ldcin < r.M))
+      return "leading dimension smaller than the stored row count";
+    if (r.lda > LDMAX || r.ldb > LDMAX || r.ldc > LDMAX || (separate && r.ldcin > LDMAX))
+      return "leading dimension above 2^24";
+    if (mixed && r.diag && (r.M != r.N || !c.dscal)) return "diag: a square problem and dscal required";
+    if (!inside(r.offa, ar, ac, r.lda, c.na) || !inside(r.offb, br, bc, r.ldb, c.nb) ||
+        !inside(r.offc, r.M, r.N, r.ldc, c.nc) ||
+        (separate && !inside(r.offcin, r.M, r.N, r.ldcin, c.ncin)) ||
+        (sca && !inside(r.offs, r.K, 1, r.K, c.ns)))
+      return "operand outside its arena";
+    cs.emplace_back(r.offc, r.offc + (r.N - 1) * r.ldc + r.M);
+    gemv = gemv && r.N == 1 && (!tb || r.K == 1);
+  }
+  std::sort(cs.begin(), cs.end());
+  for (size_t q = 1; q < cs.size(); ++q)
+    if (cs[q].first < cs[q - 1].second) return "the C regions of two problems overlap";
+  if (gemv && c.dscal) return "diagonal scalar: not with a batch that takes the GEMV kernel";
+  return "";
+}
+
+// the arguments of clrsdp_gemm_chain, checked by the caller
+struct ChainCall {
+  int form, n, nprob, halves, ncols;
+  double a1, b1, c_agg, c_in;
+  const double *A1, *B1, *C1, *A2, *DA, *DdA, *DB, *lam, *din;
+  double *O, *dot_part, *rout;
+};
+
+int chain_run(int device, const ChainCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  const int n = c.n, nb = c.nprob;
+  const int64_t nn = (int64_t)n * n * nb;  // one pointer set
+  auto up = [&](const double* h, int64_t cnt) { return h ? upload_planes<double>(mem, h, cnt) : (double*)nullptr; };
+  ChainPlan ch;
+  const bool trace = c.form == CLRSDP_CHAIN_TRACE, sym = c.form == CLRSDP_CHAIN_SYM;
+  ch.init(n, nb, c.halves, sym, sym);
+  double* O[2] = {nullptr, nullptr};
+  double *rout = nullptr, *dotp = nullptr;
+  const int64_t ndot = (int64_t)nb * cdiv(n, chain::NS), nx = (int64_t)nb * c.ncols;
+  if (trace) {
+    ch.trace = true;
+    ch.set(0, up(c.A1, nn), up(c.B1, (int64_t)n * nx), nullptr, nullptr, nullptr);
+    ch.u.ldb1 = n;
+    ch.u.sB1 = (long long)n * c.ncols;
+    ch.u.NC = c.ncols;
+    ch.u.lam = up(c.lam, nx);
+    ch.u.sLam = c.ncols;
+    ch.u.din = up(c.din, nx);
+    ch.u.rout = rout = up(c.rout, nx);
+    ch.u.sX = c.ncols;
+    ch.u.c_in = c.c_in;
+    ch.u.c_agg = c.c_agg;
+  } else {
+    for (int hf = 0; hf < c.halves; ++hf) {  // each pointer set a device allocation of its own
+      const int64_t o = hf * nn;
+      O[hf] = up(c.O + o, nn);
+      ch.set(hf, up(c.A1 + o, nn), up(c.B1 + o, nn), !sym && c.C1 ? up(c.C1 + o, nn) : nullptr,
+             up(c.A2 + o, nn), O[hf]);
+    }
+    if (c.dot_part) {
+      ch.u.DA[0] = up(c.DA, nn);
+      ch.u.DdA[0] = up(c.DdA, nn);
+      ch.u.DB[0] = up(c.DB, nn);
+      ch.u.dot_part = dotp = up(c.dot_part, ndot);
+    }
+  }
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  ch.launch(s, c.a1, c.b1);
+  HIPCHK(hipStreamSynchronize(s));
+  if (trace) download_planes<double>(rout, c.rout, nx);
+  for (int hf = 0; hf < (trace ? 0 : c.halves); ++hf) download_planes<double>(O[hf], c.O + hf * nn, nn);
+  if (dotp) download_planes<double>(dotp, c.dot_part, ndot);
+  return CLRSDP_OK;
+}
+
 int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh, const double* dMh,
                     double gamma, double* alpha, double* min_eig, std::string& err) {
   DeviceGuard dg(device);
@@ -4272,6 +4499,64 @@ int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans, 
     else if (words == 2) trsm_words<mw::dd>(device, mode, trans, nblocks, n, nrhs, A, B);
     else trsm_words<mw::qd>(device, mode, trans, nblocks, n, nrhs, A, B);
     return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_gemm(int32_t device, int32_t words, int32_t form, int32_t transa, int32_t transb,
+                    double alpha, double beta, const double* dscal, double dmult, int64_t nprob,
+                    const clrsdp_gemm_problem* prob, const double* A, int64_t na, const double* B,
+                    int64_t nb, double* C, int64_t nc, const double* Cin, int64_t ncin,
+                    const double* sa, const double* sl, int64_t ns, int32_t* path) {
+  const GemmCall c{form, transa, transb, alpha, beta, dscal, dmult, nprob, prob, A, B, Cin,
+                   form == CLRSDP_GEMM_SCALED ? sa : nullptr, form == CLRSDP_GEMM_SCALED ? sl : nullptr,
+                   C, na, nb, nc, ncin, ns};
+  const std::string bad = gemm_check(words, c);
+  if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
+  try {
+    const int pth = words == 1 ? gemm_words<double>(device, c)
+                    : words == 2 ? gemm_words<mw::dd>(device, c) : gemm_words<mw::qd>(device, c);
+    if (path) *path = pth;
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_gemm_chain(int32_t device, int32_t form, int64_t n, int64_t nprob, int32_t halves,
+                          int64_t ncols, double a1, double b1, const double* A1, const double* B1,
+                          const double* C1, const double* A2, double* O, const double* DA,
+                          const double* DdA, const double* DB, double* dot_part, const double* lam,
+                          const double* din, double c_agg, double c_in, double* rout) {
+  if (form < CLRSDP_CHAIN || form > CLRSDP_CHAIN_TRACE) { g_last_error = "unknown form"; return CLRSDP_E_ARG; }
+  if (n < 1 || n > 128) { g_last_error = "chain_f64: n must be 1 .. 128"; return CLRSDP_E_ARG; }
+  if (nprob < 1 || nprob > 4096) { g_last_error = "chain_f64: nprob must be 1 .. 4096"; return CLRSDP_E_ARG; }
+  if (halves != 1 && !(halves == 2 && form == CLRSDP_CHAIN_SYM)) {
+    g_last_error = "chain_f64: halves must be 1 (2: CHAIN_SYM only)";
+    return CLRSDP_E_ARG;
+  }
+  if (!A1 || !B1) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+  if (form == CLRSDP_CHAIN_TRACE) {
+    if (ncols < 1 || ncols > 4096) { g_last_error = "chain_f64: ncols must be 1 .. 4096"; return CLRSDP_E_ARG; }
+    if (!lam || !rout) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+  } else {
+    if (!A2 || !O) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+    if (form == CLRSDP_CHAIN_SYM && dot_part) { g_last_error = "chain_f64: no dot epilogue with CHAIN_SYM"; return CLRSDP_E_ARG; }
+    if (dot_part && (!DA || !DdA || !DB)) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+  }
+  const ChainCall c{form, (int)n, (int)nprob, halves, (int)ncols, a1, b1, c_agg, c_in, A1, B1, C1, A2,
+                    DA, DdA, DB, lam, din, O, form == CLRSDP_CHAIN ? dot_part : nullptr, rout};
+  try {
+    return chain_run(device, c);
   } catch (const ClrsdpError& e) {
     g_last_error = e.msg;
     return e.code;

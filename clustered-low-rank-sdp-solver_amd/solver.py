@@ -488,6 +488,229 @@ def trsm(blocks, rhs, mode: int, trans: bool, precision_words: int = 1, device: 
     return out
 
 
+# what gemm() and gemm_chain() put wherever a kernel must not write (a quiet NaN with a payload)
+GEMM_PAYLOAD = np.uint64(0x7FF8C0DEC0DEC0DE)
+_GEMM_FORMS = {"plain": _lib.GEMM_PLAIN, "sym": _lib.GEMM_SYM, "upper": _lib.GEMM_UPPER,
+               "scaled": _lib.GEMM_SCALED, "mixed": _lib.GEMM_MIXED}
+
+
+def _payload(shape):
+    return np.full(shape, GEMM_PAYLOAD, dtype=np.uint64).view(np.float64)
+
+
+def _limbs3(a, w, what):
+    """a matrix as raw limbs (w, rows, cols): float 2-D (trailing limbs 0), object 2-D of mpmath
+    numbers (split exactly), or raw limbs already"""
+    a = np.asarray(a)
+    if a.dtype != object and a.ndim == 3:
+        if a.shape[0] != w:
+            raise ValueError(f"{what}: raw limbs need shape (words, rows, columns)")
+        return np.asarray(a, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2:
+        raise ValueError(f"{what}: matrices expected")
+    pl = np.asarray(to_planes(a.reshape(-1, order="F"), w), dtype=np.float64).reshape(w, -1)
+    return pl.reshape((w, a.shape[1], a.shape[0])).transpose(0, 2, 1)
+
+
+@dataclass
+class GemmResult:
+    C: list            # per problem the M x N result (see gemm)
+    path: int          # the kernel (_lib.PATH_*)
+    untouched: bool    # every cell of the C arena outside the results still holds GEMM_PAYLOAD
+
+
+def gemm(A, B, Cin=None, precision_words: int = 1, form: str = "plain", transa: bool = False,
+         transb: bool = False, alpha: float = 1.0, beta: float = 0.0, dscal=None, dmult: float = 0.0,
+         ops=None, sa=None, sl=None, inplace=False, ldpad: int = 0, gaps=None, device: int = 0,
+         raw_limbs: bool = False) -> GemmResult:
+    """One batched product launch ``C_p = alpha op(A_p) op(B_p) + beta Cin_p`` through the solver's
+    GemmPlan (clrsdp_gemm, include/clrsdp.h).  ``A``, ``B`` (and ``Cin``) are lists of stored
+    matrices: float arrays, object arrays of mpmath numbers, or raw limbs (words, rows, columns).
+    ``form``: "plain", "sym", "upper", "scaled" (with the lists ``sa``, ``sl`` of K factors each) or
+    "mixed" (``ops[p] = (transa, transb, alpha, beta, diag)``).  ``inplace`` (a bool, or one per
+    problem): C starts as Cin and is updated in place; otherwise Cin is an arena of its own.
+
+    Layout.  Every arena holds the problems one after the other with leading dimension rows +
+    ``ldpad``; ``gaps[arena][p]`` ("A", "B", "C", "Cin") extra elements in front of problem p (equal
+    shapes at equal gaps make a uniform batch).  The padding rows of A, B and Cin hold NaN.  The C
+    arena has 64 guard elements at each end and holds GEMM_PAYLOAD in the guards, gaps, padding
+    rows and (unless in place) the result cells, so a cell the kernel did not write is a NaN.
+
+    Returns a :class:`GemmResult`; ``C[p]`` is a float array at words 1, else the exact limb sums
+    as mpmath numbers (``raw_limbs``: float limbs (words, M, N) as the device left them)."""
+    w = int(precision_words)
+    if form not in _GEMM_FORMS:
+        raise ValueError(f"unknown form {form!r}")
+    P = len(A)
+    if P == 0 or len(B) != P:
+        raise ValueError("one B per A, at least one problem")
+    mixed = form == "mixed"
+    if mixed and (ops is None or len(ops) != P):
+        raise ValueError("mixed: one (transa, transb, alpha, beta, diag) per problem")
+    if form == "scaled" and (sa is None or sl is None or len(sa) != P or len(sl) != P):
+        raise ValueError("scaled: one sa and one sl per problem")
+    if Cin is not None and len(Cin) != P:
+        raise ValueError("one Cin per problem")
+    inpl = list(inplace) if isinstance(inplace, (list, tuple)) else [bool(inplace)] * P
+    if len(inpl) != P or (any(inpl) and Cin is None):
+        raise ValueError("inplace: one flag per problem, and Cin to start from")
+    gaps = gaps or {}
+    G = 64
+    recs = (_lib.GemmProblem * P)()
+    arenas = {k: [] for k in ("A", "B", "C", "Cin")}
+    pos = {"A": 0, "B": 0, "C": G, "Cin": 0}
+    arenas["C"].append(_payload((w, G)))
+    cells = []
+
+    def place(name, lim, fill):
+        """append the (w, rows, cols) matrix with padded columns; returns (offset, ld)"""
+        g = int(gaps.get(name, [0] * P)[p])
+        if g:
+            arenas[name].append(fill((w, g)))
+        rows, cols = lim.shape[1:]
+        ld = rows + ldpad
+        buf = fill((w, cols, ld))
+        buf[:, :, :rows] = lim.transpose(0, 2, 1)
+        arenas[name].append(buf.reshape(w, -1))
+        off = pos[name] + g
+        pos[name] = off + ld * cols
+        return off, ld
+
+    nanfill = lambda shape: np.full(shape, np.nan)
+    svec = []
+    for p in range(P):
+        a, b = _limbs3(A[p], w, "A"), _limbs3(B[p], w, "B")
+        ta, tb = (bool(ops[p][0]), bool(ops[p][1])) if mixed else (bool(transa), bool(transb))
+        M, K = (a.shape[2], a.shape[1]) if ta else (a.shape[1], a.shape[2])
+        Kb, N = (b.shape[2], b.shape[1]) if tb else (b.shape[1], b.shape[2])
+        if K != Kb:
+            raise ValueError(f"problem {p}: op(A) is {M} x {K} but op(B) is {Kb} x {N}")
+        r = recs[p]
+        r.M, r.N, r.K = M, N, K
+        r.offa, r.lda = place("A", a, nanfill)
+        r.offb, r.ldb = place("B", b, nanfill)
+        c0 = None
+        if Cin is not None and Cin[p] is not None:
+            c0 = _limbs3(Cin[p], w, "Cin")
+            if c0.shape[1:] != (M, N):
+                raise ValueError(f"problem {p}: Cin must be {M} x {N}")
+        start = c0 if (inpl[p] and c0 is not None) else _payload((w, M, N))
+        r.offc, r.ldc = place("C", start, _payload)
+        cells.append((r.offc, r.ldc, M, N))
+        r.offcin, r.ldcin = -1, r.ldc
+        if c0 is not None and not inpl[p]:
+            r.offcin, r.ldcin = place("Cin", c0, nanfill)
+        if mixed:
+            r.transa, r.transb, r.alpha, r.beta, r.diag = int(ta), int(tb), float(ops[p][2]), \
+                float(ops[p][3]), int(bool(ops[p][4]))
+        if form == "scaled":
+            va, vl = np.asarray(sa[p], dtype=np.float64).ravel(), np.asarray(sl[p], dtype=np.float64).ravel()
+            if len(va) != K or len(vl) != K:
+                raise ValueError(f"problem {p}: sa and sl need K = {K} entries")
+            r.offs = sum(len(v[0]) for v in svec)
+            svec.append((va, vl))
+    arenas["C"].append(_payload((w, G)))
+    cat = lambda name: np.ascontiguousarray(np.concatenate(arenas[name], axis=1)) if arenas[name] else None
+    Aa, Ba, Ca, Cia = cat("A"), cat("B"), cat("C"), cat("Cin")
+    sav = np.ascontiguousarray(np.concatenate([v[0] for v in svec])) if svec else None
+    slv = np.ascontiguousarray(np.concatenate([v[1] for v in svec])) if svec else None
+    ds = None if dscal is None else np.array([float(dscal)])
+    path = C.c_int32(0)
+    opt = lambda a: None if a is None else _ptr(a)
+    _lib.check(_lib.lib().clrsdp_gemm(
+        device, w, _GEMM_FORMS[form], int(bool(transa)), int(bool(transb)), float(alpha), float(beta),
+        opt(ds), float(dmult), P, recs, _ptr(Aa), Aa.shape[1], _ptr(Ba), Ba.shape[1], _ptr(Ca),
+        Ca.shape[1], opt(Cia), 0 if Cia is None else Cia.shape[1], opt(sav), opt(slv),
+        0 if sav is None else len(sav), C.byref(path)))
+    mask = np.zeros(Ca.shape[1], dtype=bool)
+    out = []
+    for off, ld, M, N in cells:
+        idx = (off + np.arange(M)[:, None] + ld * np.arange(N)[None, :])
+        mask[idx.ravel()] = True
+        lim = Ca[:, idx]                                   # (w, M, N)
+        if raw_limbs:
+            out.append(lim.copy())
+        elif w == 1:
+            out.append(lim[0].copy())
+        else:
+            vals = from_planes(np.ascontiguousarray(lim.reshape(w, -1)).reshape(-1), M * N, w)
+            out.append(np.asarray(vals, dtype=object).reshape(M, N))
+    untouched = bool(np.all(Ca.view(np.uint64)[:, ~mask] == GEMM_PAYLOAD))
+    return GemmResult(out, int(path.value), untouched)
+
+
+def gemm_chain(form: str, A1, B1, A2=None, C1=None, a1: float = 1.0, b1: float = 0.0, dot=None,
+               halves: int = 1, lam=None, din=None, c_agg: float = 1.0, c_in: float = 0.0,
+               device: int = 0):
+    """One chain_f64 launch through the solver's ChainPlan (clrsdp_gemm_chain, include/clrsdp.h),
+    fp64, lists of n x n float blocks (n <= 128), all of one size.
+      "chain": ``O_p = A2_p (a1 A1_p B1_p + b1 C1_p)``; ``dot = (DA, DdA, DB)`` (lists of blocks)
+               adds the dot epilogue.  Returns ``(O, partials)``: the per-workgroup partial sums of
+               ``<DA + DdA, DB + O>`` in launch order (None without ``dot``).
+      "sym":   ``O_p = L_p (a1 M_p L_p^T)`` with ``A1 = M`` and ``B1 = L`` lower triangular with
+               exact zeros above the diagonal (the kernel relies on them); ``halves = 2``: the
+               second half of the lists goes to the kernel as its second pointer set.  Returns
+               ``(O, None)``.
+      "trace": ``rout[p][t] = c_agg lam[p][t] ((A1_p B1_p)[:, t] . B1_p[:, t]) + c_in din[p][t]``,
+               ``B1_p`` n x ncols; ``din`` may be None.  Returns ``(rout, None)``.
+    O and rout start as GEMM_PAYLOAD, so an entry the kernel did not write comes back a NaN."""
+    forms = {"chain": _lib.CHAIN, "sym": _lib.CHAIN_SYM, "trace": _lib.CHAIN_TRACE}
+    if form not in forms:
+        raise ValueError(f"unknown form {form!r}")
+    mats = [np.asarray(a, dtype=np.float64) for a in A1]
+    if not mats or any(a.ndim != 2 or a.shape != mats[0].shape or a.shape[0] != a.shape[1] for a in mats):
+        raise ValueError("A1: square blocks of one size")
+    n, tot = mats[0].shape[0], len(mats)
+    if halves not in (1, 2) or tot % halves:
+        raise ValueError("halves: 1 or 2, dividing the number of blocks")
+    flat = lambda lst: np.ascontiguousarray(np.concatenate(
+        [np.asarray(a, dtype=np.float64).reshape(-1, order="F") for a in lst]))
+
+    def blocks(lst, what, cols=n):
+        if lst is None or len(lst) != tot:
+            raise ValueError(f"{what}: one block per problem")
+        for a in lst:
+            if np.asarray(a).shape != (n, cols):
+                raise ValueError(f"{what}: blocks must be {n} x {cols}")
+        return flat(lst)
+
+    opt = lambda a: None if a is None else _ptr(a)
+    a1v = flat(mats)
+    if form == "trace":
+        if B1 is None or len(B1) != tot or np.asarray(B1[0]).ndim != 2:
+            raise ValueError("B1: one n x ncols block per problem")
+        nc = np.asarray(B1[0]).shape[1]
+        b1v = blocks(B1, "B1", nc)
+        def vec(lst, what):
+            if lst is None or len(lst) != tot or any(np.asarray(v).size != nc for v in lst):
+                raise ValueError(f"{what}: ncols numbers per problem")
+            return np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in lst]))
+
+        lamv = vec(lam, "lam")
+        dinv = None if din is None else vec(din, "din")
+        rout = _payload(tot * nc).copy()
+        _lib.check(_lib.lib().clrsdp_gemm_chain(
+            device, forms[form], n, tot, 1, nc, float(a1), float(b1), _ptr(a1v), _ptr(b1v), None, None,
+            None, None, None, None, None, _ptr(lamv), opt(dinv), float(c_agg), float(c_in), _ptr(rout)))
+        return [rout[p * nc:(p + 1) * nc].copy() for p in range(tot)], None
+    b1v, a2v = blocks(B1, "B1"), blocks(A2 if A2 is not None else (B1 if form == "sym" else None), "A2")
+    c1v = None if C1 is None or form == "sym" else blocks(C1, "C1")
+    O = _payload(tot * n * n).copy()
+    dv, part = [None] * 3, None
+    if dot is not None:
+        if form != "chain" or len(dot) != 3:
+            raise ValueError("dot = (DA, DdA, DB), with the chain form only")
+        dv = [blocks(d, "dot") for d in dot]
+        part = _payload(tot * (-(-n // 32))).copy()
+    _lib.check(_lib.lib().clrsdp_gemm_chain(
+        device, forms[form], n, tot // halves, halves, 0, float(a1), float(b1), _ptr(a1v), _ptr(b1v),
+        opt(c1v), _ptr(a2v), _ptr(O), opt(dv[0]), opt(dv[1]), opt(dv[2]), opt(part), None, None, 0.0,
+        0.0, None))
+    return [O[p * n * n:(p + 1) * n * n].reshape((n, n), order="F").copy() for p in range(tot)], part
+
+
 def initial_point(bi: BlockInfo, omega_p, omega_d):
     """x = 0, X = omega_p I, y = 0, Y = omega_d I (MPMP.jl:660-686)."""
     x = np.zeros(sum(bi.dim_S))

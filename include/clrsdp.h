@@ -376,6 +376,125 @@ int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans,
                     int64_t nblocks, const int64_t* n, const int64_t* nrhs,
                     const double* A, double* B);
 
+/* One batched product launch, C_p = alpha op(A_p) op(B_p) + beta C_in,p (+ dmult * *dscal on the
+ * diagonal), through the solver's own GemmPlan (the products of every stage: X^-1, R, the Schur
+ * pairings V^T X^-1 V, W_j, Q, the weighted A, the directions), at fp64 (words 1), double-double
+ * (2) or quad-double (4).  The plan is built from the records below exactly as build_plans()
+ * builds the solver's, finalised and launched once on a stream of the call's own; *path (may be
+ * NULL) receives the kernel that the plan's launch selected.
+ *
+ * Buffers.  A, B, C, C_in, and sa / sl are arenas of na, nb, nc, ncin and ns numbers, each as
+ * `words` planes (hi limb first).  Problem p's operands start at the element offsets offa, offb,
+ * offc, offcin (and offs into sa and sl) and are column-major with the leading dimensions lda,
+ * ldb, ldc, ldcin.  Stored shapes: A is M x K (transa: K x M), B is K x N (transb: N x K), C and
+ * C_in are M x N; every leading dimension is at least the stored row count and at most 2^24.  A
+ * and B are read only inside the stored rows (rows between the row count and the leading
+ * dimension are never loaded).  The whole C arena is copied to the device before the launch and
+ * back after it, so whatever the caller puts into the padding rows, the gaps between problems and
+ * the ends of the arena comes back bitwise unless a kernel wrote there.  The C regions of two
+ * problems (offc .. offc + (N - 1) ldc + M) must not overlap.  The offsets decide the kernel at
+ * fp64: equal shapes, leading dimensions and constant offset differences in every arena make a
+ * uniform batch (gemm_f64_uni), anything else goes through descriptors (gemm_f64_lds).
+ *
+ * C_in.  beta = 0: C_in is not read.  Otherwise problem p reads C_in at offcin, or, when the
+ * C_in arena is NULL or the problem's offcin is negative, its own C in place (ldcin is then
+ * ignored), as R -= dX dY does.
+ *
+ * form
+ *   CLRSDP_GEMM_PLAIN   GemmPlan::add.
+ *   CLRSDP_GEMM_SYM     add with sym = true (fp64, square, op(A) = A, beta = 0, no dscal): the
+ *                       product is symmetric in exact arithmetic (L^-1 dM L^-T); only the lower
+ *                       tiles are computed, each is written with its mirror image and a diagonal
+ *                       tile mirrors its lower triangle, so C is exactly symmetric.
+ *   CLRSDP_GEMM_UPPER   add with upper = true (multi-word, square): only the 8 x 8 tiles on and
+ *                       above the diagonal are computed; tiles strictly below it are not written.
+ *   CLRSDP_GEMM_SCALED  add_scaled (fp64, transa = 0, transb = 1): op(A) = A diag(sa .* sl), the
+ *                       K factors of problem p at sa + offs, sl + offs.
+ *   CLRSDP_GEMM_MIXED   add_op (fp64): transa, transb, alpha and beta are each record's own (the
+ *                       call's are ignored); a record with diag != 0 (square) adds *dscal, once,
+ *                       to its diagonal (the kernel's flags bit 4; dmult is ignored).
+ * dscal (may be NULL; fp64 only): one number in host memory; PLAIN and SCALED add dmult * *dscal
+ * to C(i, i) of every problem (GemmPlan::launch's dscal, as R = mu I - X Y uses it).  Not with a
+ * batch that takes the GEMV kernel.
+ *
+ * *path: the kernel, derived by GemmPlan::path() from the fields launch() branches on.  A batch
+ * whose problems all have N = 1 (and, with transb, K = 1) takes gemv_batched, one of its five
+ * code paths; a MIXED or SCALED batch never does. */
+#define CLRSDP_GEMM_PLAIN 0
+#define CLRSDP_GEMM_SYM 1
+#define CLRSDP_GEMM_UPPER 2
+#define CLRSDP_GEMM_SCALED 3
+#define CLRSDP_GEMM_MIXED 4
+
+#define CLRSDP_PATH_GEMV_N_F64 1  /* gemv_batched fp64, op(A) = A: 32 loads in flight, 128-k steps */
+#define CLRSDP_PATH_GEMV_T_F64 2  /* gemv_batched fp64, op(A) = A^T: 16-lane sums, 128 / 32 / 16 k */
+#define CLRSDP_PATH_GEMV_N_MW 3   /* gemv_batched multi-word, op(A) = A: 32-k steps, then 4         */
+#define CLRSDP_PATH_GEMV_T_QD 4   /* gemv_batched quad-double A^T: thread per column ("deep")       */
+#define CLRSDP_PATH_GEMV_T_DD 5   /* gemv_batched double-double A^T: the 16-lane reduction           */
+#define CLRSDP_PATH_UNI64 6       /* gemm_f64_uni, 64 x 64 tiles                                     */
+#define CLRSDP_PATH_UNI32 7       /* gemm_f64_uni, 32 x 32 tiles (CLRSDP_GEMM_TS32_BELOW)            */
+#define CLRSDP_PATH_LDS 8         /* gemm_f64_lds (descriptors; 64 x 64 tiles)                       */
+#define CLRSDP_PATH_DYN 9         /* gemm_f64_dyn (MIXED)                                            */
+#define CLRSDP_PATH_VALU_KS 10    /* gemm_valu_ks (multi-word, 8 x 8 tiles)                          */
+
+typedef struct {
+  int64_t M, N, K;                   /* 1 .. 4096 each                                          */
+  int64_t lda, ldb, ldc, ldcin;
+  int64_t offa, offb, offc, offcin;  /* element offsets into the arenas; offcin < 0: in place    */
+  int64_t offs;                      /* SCALED: offset of the K factors in sa and sl             */
+  int32_t transa, transb, diag;      /* MIXED only                                               */
+  int32_t reserved;
+  double alpha, beta;                /* MIXED only                                               */
+} clrsdp_gemm_problem;
+
+/* Refused with CLRSDP_E_ARG before any device work: a NULL prob, A, B or C; nprob outside
+ * 1 .. 65536; M, N or K outside 1 .. 4096 (K = 0 in particular: the tiled kernels clamp their
+ * loads to index K - 1); a leading dimension below its stored row count; SYM or UPPER on a
+ * non-square problem; SYM, SCALED, MIXED or dscal with words != 1; UPPER with words = 1; SCALED
+ * other than transa = 0, transb = 1, or without sa and sl; SYM with transa, beta != 0 or dscal;
+ * a diag record that is not square or comes without dscal; an operand that does not lie inside
+ * its arena; overlapping C regions. */
+int32_t clrsdp_gemm(int32_t device, int32_t words, int32_t form, int32_t transa, int32_t transb,
+                    double alpha, double beta, const double* dscal, double dmult, int64_t nprob,
+                    const clrsdp_gemm_problem* prob, const double* A, int64_t na, const double* B,
+                    int64_t nb, double* C, int64_t nc, const double* Cin, int64_t ncin,
+                    const double* sa, const double* sl, int64_t ns, int32_t* path);
+
+/* One chain_f64 launch through the solver's ChainPlan: fp64, nprob blocks of n x n (1 <= n <= 128)
+ * per pointer set, block p of every array at element offset p n^2, leading dimension n.
+ *   CLRSDP_CHAIN        O_p = A2_p (a1 A1_p B1_p + b1 C1_p); C1 may be NULL (no second term).
+ *                       Z = X^-1 (P Y - R) is (a1, b1) = (1, -1), dY = X^-1 (R - dX Y) is (-1, 1).
+ *                       With dot_part != NULL (then DA, DdA, DB are required, nprob n^2 each) the
+ *                       launch also leaves the raw per-workgroup partial sums of
+ *                       <DA + DdA, DB + O>: nprob * ceil(n / 32) numbers, workgroup b (strip
+ *                       b / nprob of problem b % nprob) at dot_part[b]; their sum is the dot
+ *                       product over all blocks.  O is bitwise the same with and without.
+ *   CLRSDP_CHAIN_SYM    O_p = L_p (M_p L_p^T) with A1 = M, B1 = A2 = L (the caller passes L as
+ *                       both), C1 ignored, a1 scales the inner product.  L MUST be lower
+ *                       triangular with exact zeros above its diagonal: the kernel stops the inner
+ *                       sums of strip s at k = 32 (s + 1) and skips the row tiles above the strip on
+ *                       the strength of those zeros, and it does not check them.  The strip's lower
+ *                       part and its mirror image are written: O is exactly symmetric.  halves = 2:
+ *                       two pointer sets in one launch (L_X^-1 dX L_X^-T and L_Y^-1 dY L_Y^-T of
+ *                       the step length): every array holds 2 nprob blocks, and the second nprob of
+ *                       them are given to the kernel as a device allocation of their own.
+ *   CLRSDP_CHAIN_TRACE  rout[p][t] = c_agg lam[p][t] ((A1_p B1_p)[:, t] . B1_p[:, t]) + c_in din[p][t]
+ *                       for t < ncols: A1_p is n x n (Z), B1_p is n x ncols (V, leading dimension n,
+ *                       problem p at offset p n ncols), lam, din, rout hold ncols numbers per
+ *                       problem; din may be NULL.  1 <= ncols <= 4096.  A2, O are not used.
+ * O (and rout, dot_part) are copied to the device before the launch and back after it.
+ * Refused with CLRSDP_E_ARG before any device work: n outside 1 .. 128, nprob outside 1 .. 4096,
+ * halves other than 1 (2: CHAIN_SYM only), an unknown form, ncols out of range, a NULL required
+ * buffer. */
+#define CLRSDP_CHAIN 0
+#define CLRSDP_CHAIN_SYM 1
+#define CLRSDP_CHAIN_TRACE 2
+int32_t clrsdp_gemm_chain(int32_t device, int32_t form, int64_t n, int64_t nprob, int32_t halves,
+                          int64_t ncols, double a1, double b1, const double* A1, const double* B1,
+                          const double* C1, const double* A2, double* O, const double* DA,
+                          const double* DdA, const double* DB, double* dot_part, const double* lam,
+                          const double* din, double c_agg, double c_in, double* rout);
+
 #ifdef __cplusplus
 }
 #endif
