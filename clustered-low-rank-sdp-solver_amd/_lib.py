@@ -39,7 +39,8 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_comm_unique_id", "clrsdp_comm_init", "clrsdp_save_state",
            "clrsdp_restore_state", "clrsdp_step_length", "clrsdp_set_factorization",
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
-           "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain"]
+           "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
+           "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state"]
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -52,6 +53,10 @@ PATH_NAMES = {1: "gemv_batched fp64 N", 2: "gemv_batched fp64 T", 3: "gemv_batch
               6: "gemm_f64_uni 64", 7: "gemm_f64_uni 32", 8: "gemm_f64_lds", 9: "gemm_f64_dyn",
               10: "gemm_valu_ks"}
 CHAIN, CHAIN_SYM, CHAIN_TRACE = range(3)
+# clrsdp_reduce kinds and ops, the workgroups (and partials) of flat_reduce and update_state
+RED_FLAT_FOLD, RED_FLAT_TREE, RED_VEC, RED_FOLD, RED_ORDERED = range(5)
+OP_DOT, OP_DOTSUM, OP_SUM, OP_MAX, OP_MIN, OP_MAXABS = range(6)
+RED_G = 256
 
 P_i64 = C.POINTER(C.c_int64)
 P_i32 = C.POINTER(C.c_int32)
@@ -96,6 +101,11 @@ class GemmProblem(C.Structure):
                 ("offb", C.c_int64), ("offc", C.c_int64), ("offcin", C.c_int64), ("offs", C.c_int64),
                 ("transa", C.c_int32), ("transb", C.c_int32), ("diag", C.c_int32),
                 ("reserved", C.c_int32), ("alpha", C.c_double), ("beta", C.c_double)]
+
+
+class Fold(C.Structure):
+    _fields_ = [("cnt", C.c_int64), ("stride", C.c_int64), ("off", C.c_int64), ("op", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p)
@@ -154,6 +164,15 @@ def lib():
     L.clrsdp_gemm_chain.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
                                     C.c_double, C.c_double] + [P_f64] * 11 + [C.c_double, C.c_double,
                                                                              P_f64]
+    L.clrsdp_reduce.argtypes = [C.c_int32] * 4 + [C.c_int64, C.c_int64] + [P_f64] * 4 + \
+        [C.c_int64, C.POINTER(Fold), P_f64, P_f64]
+    L.clrsdp_slab_sum.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, P_f64, P_f64,
+                                  C.c_double, C.c_double, P_f64, C.c_int64, P_f64, P_f64, C.c_int64,
+                                  C.c_int64]
+    L.clrsdp_update_state.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [P_f64] * 4 + \
+        [C.c_int64] + [P_f64] * 3 + [C.c_int64] + [P_f64] * 3 + [C.c_int64, P_i32, P_f64, P_f64,
+                                                                 C.c_int64, P_f64, P_f64, P_f64,
+                                                                 C.c_int32, P_f64, P_f64]
     L.clrsdp_step_length.argtypes = [C.c_int32, C.c_int64, P_i64, P_f64, P_f64, C.c_double, P_f64,
                                      P_f64]
     for name in EXPORTS:

@@ -1112,6 +1112,75 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
   }
 };
 
+// ---- the launches of the reductions, the slab sums and the state update: one place for each
+// kernel's grid, block, LDS size and op mapping, shared by the Solver's stages and by
+// clrsdp_reduce / clrsdp_slab_sum / clrsdp_update_state
+constexpr int RED_G = 256;  // fixed chunking of the flat reductions (deterministic)
+
+// per-workgroup partials of sum a.*b (op 0), sum (a+da).*(b+db) (1) or max |a| (2) -> part[RED_G]
+template <class T>
+void launch_flat_reduce(hipStream_t s, const T* A, const T* B_, const T* dA, const T* dB,
+                        long long n, int op, T* part) {
+  flat_reduce<T><<<RED_G, 256, 0, s>>>(A, B_, dA, dB, n, op, part);
+}
+// one workgroup: sum a.*b (op 0), max |a| (2) or sum a (3) over [0, n) -> *dst
+template <class T>
+void launch_vec_reduce(hipStream_t s, const T* a, const T* b, long long n, int op, T* dst) {
+  vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, s>>>(a, b, n, op, dst);
+}
+// one-workgroup fixed-tree reduction of n partials of a flat op (sum, or max for op 2)
+template <class T>
+void launch_vec_reduce_tree(hipStream_t s, const T* in, int n, int op, T* dst) {
+  launch_vec_reduce<T>(s, in, in, n, op == 2 ? 2 : 3, dst);
+}
+// the fold of RED_G flat_reduce partials of a flat op, as blk_dot queues it
+template <class T>
+FoldRed<T> flat_fold(const T* part, int op, int dst) {
+  return FoldRed<T>{part, 1, RED_G, op == 2 ? 2 : 0, dst, 0};
+}
+// the pending folds in scalar_kernel launches of at most six; the last launch runs the scalar
+// logic `which` (-1: none), the first one clears p.zero_n status words.  No fold: one launch.
+template <class T>
+void launch_folds(hipStream_t s, T* sc, ScalarParams<T> p, const std::vector<FoldRed<T>>& pend,
+                  int which) {
+  size_t q = 0;
+  while (q < pend.size() || q == 0) {
+    const size_t cnt = std::min<size_t>(6, pend.size() - q);
+    p.nred = (int)cnt;
+    for (size_t i = 0; i < cnt; ++i) p.red[i] = pend[q + i];
+    q += cnt;
+    const bool last = q >= pend.size();
+    scalar_kernel<T><<<1, 64, 0, s>>>(sc, p, last ? which : -1);
+    p.zero_n = 0;
+    if (last) break;
+  }
+}
+template <class T>
+void launch_ordered_reduce(hipStream_t s, const T* in, int cnt, long long stride, int op, T* out) {
+  ordered_reduce<T><<<1, 1, 0, s>>>(in, cnt, stride, op, out);
+}
+template <class T>
+void launch_slab_sum4(hipStream_t s, const T* in, int cnt, long long stride, long long n, T* out,
+                      const T* base = nullptr, double cbase = 0.0, double csum = 1.0,
+                      T* out2 = nullptr) {
+  slab_sum4<T><<<cdiv(n, 64), 256, 0, s>>>(in, cnt, stride, n, out, base, cbase, csum, out2);
+}
+inline size_t slab_qsolve_lds(long long n) { return ((size_t)n + 256) * sizeof(double); }
+inline void launch_slab_qsolve(hipStream_t s, const double* in, int cnt, long long stride, int n,
+                               const double* base, double cbase, double csum, const double* Q,
+                               int ldq, double* out) {
+  slab_qsolve<<<cdiv(n, 64), 256, slab_qsolve_lds(n), s>>>(in, cnt, stride, n, base, cbase, csum, Q,
+                                                           ldq, out);
+}
+template <class T>
+void launch_update_state(hipStream_t s, T* X, const T* dX, T* Y, const T* dY, long long nel, T* x,
+                         const T* dx, long long nx, const T* cv, T* y, const T* dy, long long ny,
+                         const T* bv, const T* alpha_p, const T* alpha_d, const int* info, int ninfo,
+                         T* part, const StepAlpha<T>& sa) {
+  update_state<T><<<RED_G, 256, 0, s>>>(X, dX, Y, dY, nel, x, dx, nx, cv, y, dy, ny, bv, alpha_p,
+                                        alpha_d, info, ninfo, part, sa);
+}
+
 struct HandleBase {
   std::string err;
   int dev = 0;  // the handle's HIP device (every C-ABI call on the handle runs with it current)
@@ -2516,24 +2585,13 @@ struct Solver final : HandleBase {
     p.guard = info;
     p.nguard = info_count;
     zero_info = false;
-    size_t q = 0;
-    while (q < pend.size() || q == 0) {  // at most 6 folded reductions per launch
-      const size_t cnt = std::min<size_t>(6, pend.size() - q);
-      p.nred = (int)cnt;
-      for (size_t i = 0; i < cnt; ++i) p.red[i] = pend[q + i];
-      q += cnt;
-      const bool last = q >= pend.size();
-      scalar_kernel<T><<<1, 64, 0, stream>>>(sc, p, last ? which : -1);
-      p.zero_n = 0;
-      if (last) break;
-    }
+    launch_folds<T>(stream, sc, p, pend, which);  // at most 6 folded reductions per launch
     pend.clear();
   }
   // local block-sum (op 0/1) or block-max (op 2) into *dst
-  static constexpr int RED_G = 256;  // fixed chunking of the flat reductions (deterministic)
   void local_blk_reduce(const T* A, const T* B_, const T* dA, const T* dB, int op, T* dst) {
     if (nb()) {
-      flat_reduce<T><<<RED_G, 256, 0, stream>>>(A, B_, dA, dB, nblk_el, op, bpart);
+      launch_flat_reduce<T>(stream, A, B_, dA, dB, nblk_el, op, bpart);
       vec_reduce_tree(bpart, RED_G, op, dst);
     } else {
       fill(dst, 0.0, 1);
@@ -2542,7 +2600,7 @@ struct Solver final : HandleBase {
 
   // one-workgroup fixed-tree reduction of n <= 256 partials
   void vec_reduce_tree(const T* in, int n, int op, T* dst) {
-    vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, stream>>>(in, in, n, op == 2 ? 2 : 3, dst);
+    launch_vec_reduce_tree<T>(stream, in, n, op, dst);
   }
 
   // trace_A with the products U already in TX -> val (tval) -> aggregate
@@ -2594,8 +2652,8 @@ struct Solver final : HandleBase {
   void blk_dot(const T* A, const T* B_, const T* dA, const T* dB, int op, int slot, int tag,
                const T* part = nullptr) {
     if (world == 1 && nb()) {
-      if (!part) flat_reduce<T><<<RED_G, 256, 0, stream>>>(A, B_, dA, dB, nblk_el, op, bpart);
-      fold(part ? part : bpart, RED_G, op == 2 ? 2 : 0, slot);  // folded into the next scalar launch
+      if (!part) launch_flat_reduce<T>(stream, A, B_, dA, dB, nblk_el, op, bpart);
+      pend.push_back(flat_fold<T>(part ? part : bpart, op, slot));  // folded into the next scalar launch
       return;
     }
     if (part && nb()) vec_reduce_tree(part, RED_G, op, xsend);
@@ -2815,12 +2873,12 @@ struct Solver final : HandleBase {
     T* q_dual = !reg_Q && Qf ? Qf : nullptr;
     qf_fresh = q_dual != nullptr;
     if (world == 1 && nc()) {
-      slab_sum4<T><<<cdiv(q2, 64), 256, 0, stream>>>(Qslab, nc(), q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
+      launch_slab_sum4<T>(stream, Qslab, nc(), q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
     } else {
-      if (nc()) slab_sum4<T><<<cdiv(q2, 64), 256, 0, stream>>>(Qslab, nc(), q2, q2, xsend);
+      if (nc()) launch_slab_sum4<T>(stream, Qslab, nc(), q2, q2, xsend);
       else fill(xsend, 0.0, q2);
       exchange(2, q2);
-      slab_sum4<T><<<cdiv(q2, 64), 256, 0, stream>>>(xrecv, world, q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
+      launch_slab_sum4<T>(stream, xrecv, world, q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
     }
   }
   void factor_q() {
@@ -2873,7 +2931,7 @@ struct Solver final : HandleBase {
     // p partial = sum_j B_j^T x_j (slabs) ; local maxima of |P| and |d| into tmpsc[0..1]
     p_Btx.launch(stream, 1.0, 0.0);
     local_blk_reduce(P, nullptr, nullptr, nullptr, 2, tmpsc);
-    if (nx > 0) vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, stream>>>(dvec, nullptr, nx, 2, tmpsc + 1);
+    if (nx > 0) launch_vec_reduce<T>(stream, dvec, nullptr, nx, 2, tmpsc + 1);
     else fill(tmpsc + 1, 0.0, 1);
   }
   // defer (a loop body at one rank): the three error maxima are only read by the log and the
@@ -2884,18 +2942,18 @@ struct Solver final : HandleBase {
   void residuals_finish(bool defer = false) {
     const int64_t k = n_y + 2;
     if (world == 1 && nc()) {  // p = b - sum_j B_j^T x_j in one launch; maxima folded
-      slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, pvec, bvec, 1.0, -1.0);
+      launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, pvec, bvec, 1.0, -1.0);
       fold(tmpsc, 1, 2, SC_ERR_PMAT);
       fold(tmpsc + 1, 1, 2, SC_ERR_DVEC);
       fold(pvec, (int)n_y, 4, SC_ERR_PVEC);
       if (!defer) flush_scalars();
       return;
     }
-    if (nc()) slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, xsend);
+    if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
     else fill(xsend, 0.0, n_y);
     vlin(xsend + n_y, tmpsc, 1.0, nullptr, 0, nullptr, 0, 2);
     exchange(3, k);
-    slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(xrecv, world, k, n_y, uvec);
+    launch_slab_sum4<T>(stream, xrecv, world, k, n_y, uvec);
     vlin(pvec, bvec, 1.0, uvec, -1.0, nullptr, 0, n_y);      // p = b - sum B^T x
     reduce_ranks(k, n_y, 2, SC_ERR_PMAT);
     reduce_ranks(k, n_y + 1, 2, SC_ERR_DVEC);
@@ -2984,7 +3042,7 @@ struct Solver final : HandleBase {
         const double* src = pslab;
         int cnt = nc() * cls_nrb;
         if (world > 1) {
-          slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, cnt, n_y, n_y, xsend);
+          launch_slab_sum4<T>(stream, pslab, cnt, n_y, n_y, xsend);
           exchange(tag, n_y);
           src = xrecv;
           cnt = world;
@@ -2993,8 +3051,7 @@ struct Solver final : HandleBase {
           HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
           pending_q = false;
         }
-        slab_qsolve<<<cdiv(n_y, 64), 256, ((size_t)n_y + 256) * sizeof(double), stream>>>(
-            src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
+        launch_slab_qsolve(stream, src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
         cl_solve_dx<<<g, 256, 0, stream>>>(d_cls, cls_nrb, (int)n_y, dyv);
         HIPCHK(hipGetLastError());
         return;
@@ -3017,7 +3074,7 @@ struct Solver final : HandleBase {
     // (slab_qsolve)
     bool fused_done = false;
     if constexpr (std::is_same<T, double>::value) {
-      const size_t lds = ((size_t)n_y + 256) * sizeof(double);
+      const size_t lds = slab_qsolve_lds(n_y);
       // every workgroup re-forms all of r: cdiv(n_y, 64) x cnt x n_y slab reads in all.  Fused
       // only while those stay small (C3: 2 x 64 x 128); otherwise slab_sum4 forms r once
       const long long cnt_x = (world == 1 && nc()) ? nc() : world;
@@ -3026,7 +3083,7 @@ struct Solver final : HandleBase {
         const double* src = pslab;
         int cnt = nc();
         if (!(world == 1 && nc())) {
-          if (nc()) slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, xsend);
+          if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
           else fill(xsend, 0.0, n_y);
           exchange(tag, n_y);
           src = xrecv;
@@ -3036,8 +3093,7 @@ struct Solver final : HandleBase {
           HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
           pending_q = false;
         }
-        slab_qsolve<<<cdiv(n_y, 64), 256, lds, stream>>>(src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0,
-                                                          Qinv, (int)n_y, dyv);
+        launch_slab_qsolve(stream, src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
         HIPCHK(hipGetLastError());
         fused_done = true;
       }
@@ -3046,12 +3102,12 @@ struct Solver final : HandleBase {
       // r = p - sum_j W_j^T t_j  (-> uvec with the explicit Q^-1, -> dyv for the two solves)
       T* rv = (reg_Q || q_split) ? uvec : dyv;
       if (world == 1 && nc()) {  // one launch
-        slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, rv, pvec, 1.0, -1.0);
+        launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, rv, pvec, 1.0, -1.0);
       } else {
-        if (nc()) slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, xsend);
+        if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
         else fill(xsend, 0.0, n_y);
         exchange(tag, n_y);
-        slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(xrecv, world, n_y, n_y, rv, pvec, 1.0, -1.0);
+        launch_slab_sum4<T>(stream, xrecv, world, n_y, n_y, rv, pvec, 1.0, -1.0);
       }
       if (pending_q) {  // L_Q^-1 and Q^-1 are being computed on the side stream (iterate)
         HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
@@ -3080,12 +3136,12 @@ struct Solver final : HandleBase {
     tl_t.launch(stream, false);               // t_j = L_j^-1 t_j
     lq_Wt.launch(stream, 1.0, 0.0);           // slab_j = W2_j^T t_j  (B_j^T U_j^-1 t_j)
     if (world == 1 && nc()) {
-      slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, uvec, pvec, 1.0, -1.0);
+      launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, uvec, pvec, 1.0, -1.0);
     } else {
-      if (nc()) slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(pslab, nc(), n_y, n_y, xsend);
+      if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
       else fill(xsend, 0.0, n_y);
       exchange(tag, n_y);
-      slab_sum4<T><<<cdiv(n_y, 64), 256, 0, stream>>>(xrecv, world, n_y, n_y, uvec, pvec, 1.0, -1.0);
+      launch_slab_sum4<T>(stream, xrecv, world, n_y, n_y, uvec, pvec, 1.0, -1.0);
     }
     if (pending_q) {
       HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
@@ -3155,8 +3211,8 @@ struct Solver final : HandleBase {
       fold(eigY, nb(), 3, SC_MINEIG_Y);
     } else {
       if (nb()) {
-        ordered_reduce<T><<<1, 1, 0, stream>>>(eigX, nb(), 1, 3, xsend);
-        ordered_reduce<T><<<1, 1, 0, stream>>>(eigY, nb(), 1, 3, xsend + 1);
+        launch_ordered_reduce<T>(stream, eigX, nb(), 1, 3, xsend);
+        launch_ordered_reduce<T>(stream, eigY, nb(), 1, 3, xsend + 1);
       } else {
         fill(xsend, 1e300, 2);  // no local blocks: neutral element of min
       }
@@ -3173,11 +3229,11 @@ struct Solver final : HandleBase {
   void objectives(const clrsdp_params* prm, int pd_feas, int which = 3) {
     zero_cy = !hasC;
     if (world == 1) {
-      if (nx > 0) vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, stream>>>(cvec, x, nx, 0, sc + SC_DOT_CX);
+      if (nx > 0) launch_vec_reduce<T>(stream, cvec, x, nx, 0, sc + SC_DOT_CX);
       else fill(sc + SC_DOT_CX, 0.0, 1);
       if (hasC) local_blk_reduce(Cm, Y, nullptr, nullptr, 0, sc + SC_DOT_CY);
     } else {
-      if (nx > 0) vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, stream>>>(cvec, x, nx, 0, xsend);
+      if (nx > 0) launch_vec_reduce<T>(stream, cvec, x, nx, 0, xsend);
       else fill(xsend, 0.0, 1);
       if (hasC) local_blk_reduce(Cm, Y, nullptr, nullptr, 0, xsend + 1);
       else fill(xsend + 1, 0.0, 1);
@@ -3185,7 +3241,7 @@ struct Solver final : HandleBase {
       reduce_ranks(2, 0, 0, SC_DOT_CX);
       reduce_ranks(2, 1, 0, SC_DOT_CY);
     }
-    vec_reduce<T><<<1, vec_reduce_threads<T>(), 0, stream>>>(bvec, y, n_y, 0, sc + SC_DOT_BY);
+    launch_vec_reduce<T>(stream, bvec, y, n_y, 0, sc + SC_DOT_BY);
     scalars(prm, pd_feas, which);
     zero_cy = false;
   }
@@ -3207,9 +3263,8 @@ struct Solver final : HandleBase {
       sa.pdslot = SC_PDFEAS;
       alpha_fused = false;
     }
-    update_state<T><<<RED_G, 256, 0, stream>>>(X, dX, Y, dY, nblk_el, x, dx, nx, cvec, y, dyv, n_y,
-                                               bvec, sc + SC_ALPHA_P, sc + SC_ALPHA_D, info,
-                                               info_count, upart, sa);
+    launch_update_state<T>(stream, X, dX, Y, dY, nblk_el, x, dx, nx, cvec, y, dyv, n_y, bvec,
+                           sc + SC_ALPHA_P, sc + SC_ALPHA_D, info, info_count, upart, sa);
     if (world == 1 && !hasC) {  // the objectives from the partials, folded into one scalar launch
       zero_cy = true;
       fold(upart + RED_G, RED_G, 0, SC_DOT_CX);
@@ -3223,7 +3278,7 @@ struct Solver final : HandleBase {
   // <X,Y> partials of the current state, as update_state leaves them (after a state change
   // from the host: set_state, restore_state)
   void refresh_xy_part() {
-    flat_reduce<T><<<RED_G, 256, 0, stream>>>(X, Y, nullptr, nullptr, nblk_el, 0, upart);
+    launch_flat_reduce<T>(stream, X, Y, nullptr, nullptr, nblk_el, 0, upart);
     HIPCHK(hipGetLastError());
   }
 
@@ -4239,6 +4294,264 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
   return CLRSDP_OK;
 }
 
+// ---- clrsdp_reduce / clrsdp_slab_sum / clrsdp_update_state: the launch helpers above on planes
+struct StreamOwner {
+  hipStream_t s = nullptr;
+  StreamOwner() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ~StreamOwner() { (void)hipStreamDestroy(s); }
+};
+template <class T>
+T from_limbs(const double* l) {
+  T v = T(l[0]);
+  for (int i = 1; i < Num<T>::W; ++i) v += T(l[i]);
+  return v;
+}
+
+// the kernel's own code of a public op for a kind, or -1 where the solver never issues the pair
+int reduce_op_code(int kind, int op) {
+  switch (kind) {
+    case CLRSDP_RED_FLAT_FOLD:
+    case CLRSDP_RED_FLAT_TREE:  // flat_reduce: 0 dot, 1 dot of sums, 2 max |a|
+      return op == CLRSDP_OP_DOT ? 0 : op == CLRSDP_OP_DOTSUM ? 1 : op == CLRSDP_OP_MAXABS ? 2 : -1;
+    case CLRSDP_RED_VEC:  // vec_reduce: 0 dot, 2 max |a| (3, the plain sum, is the tree's)
+      return op == CLRSDP_OP_DOT ? 0 : op == CLRSDP_OP_MAXABS ? 2 : -1;
+    case CLRSDP_RED_FOLD:  // FoldRed: 0 sum, 2 max, 3 min, 4 max |.|
+      return op == CLRSDP_OP_SUM ? 0 : op == CLRSDP_OP_MAX ? 2 : op == CLRSDP_OP_MIN ? 3
+             : op == CLRSDP_OP_MAXABS ? 4 : -1;
+    case CLRSDP_RED_ORDERED:  // ordered_reduce: the solver takes minima with it (op 3)
+      return op == CLRSDP_OP_MIN ? 3 : -1;
+  }
+  return -1;
+}
+
+struct ReduceCall {
+  int kind, op;
+  int64_t n, stride;
+  const double *a, *b, *da, *db;
+  int64_t nfold;
+  const clrsdp_fold* folds;
+  double *out, *part;
+};
+
+constexpr int64_t RED_MAX_N = 1LL << 28;
+
+std::string reduce_check(int words, const ReduceCall& c) {
+  if (words != 1 && words != 2 && words != 4) return "words must be 1, 2 or 4";
+  if (c.kind < CLRSDP_RED_FLAT_FOLD || c.kind > CLRSDP_RED_ORDERED) return "unknown kind";
+  if (!c.a || !c.out) return "null argument";
+  if (c.n < 1 || c.n > RED_MAX_N) return "n out of range";
+  if (c.kind == CLRSDP_RED_FOLD) {
+    if (c.nfold < 1 || c.nfold > 12 || !c.folds) return "FOLD: 1 .. 12 folds";
+    for (int64_t q = 0; q < c.nfold; ++q) {
+      const clrsdp_fold& f = c.folds[q];
+      if (reduce_op_code(c.kind, f.op) < 0) return "FOLD: op must be sum, max, min or max-abs";
+      if (f.cnt < 1 || f.cnt > c.n || f.stride < 1 || f.stride > c.n || f.off < 0 || f.off >= c.n ||
+          f.off + (f.cnt - 1) * f.stride >= c.n)
+        return "FOLD: a fold does not lie inside the source";
+    }
+    if (c.part) return "part: FLAT kinds only";
+    return "";
+  }
+  if (c.nfold != 0 || c.folds) return "folds: FOLD only";
+  if (reduce_op_code(c.kind, c.op) < 0) return "the solver issues no such op with this kind";
+  if (c.kind == CLRSDP_RED_ORDERED) {
+    if (c.stride < 1 || c.stride > RED_MAX_N || (c.n - 1) * c.stride + 1 > RED_MAX_N)
+      return "ORDERED: stride out of range";
+    if (c.part) return "part: FLAT kinds only";
+    return "";
+  }
+  if (c.stride != 1) return "stride: 1 with this kind";
+  if (c.op != CLRSDP_OP_MAXABS && !c.b) return "null argument";
+  if (c.op == CLRSDP_OP_DOTSUM && (!c.da || !c.db)) return "null argument";
+  if (c.part && c.kind == CLRSDP_RED_VEC) return "part: FLAT kinds only";
+  return "";
+}
+
+template <class T>
+void reduce_words(int device, const ReduceCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  const int code = c.kind == CLRSDP_RED_FOLD ? 0 : reduce_op_code(c.kind, c.op);
+  const int64_t na = c.kind == CLRSDP_RED_ORDERED ? (c.n - 1) * c.stride + 1 : c.n;
+  const int64_t nout = c.kind == CLRSDP_RED_FOLD ? c.nfold : 1;
+  const bool flat = c.kind == CLRSDP_RED_FLAT_FOLD || c.kind == CLRSDP_RED_FLAT_TREE;
+  const T* a = upload_planes<T>(mem, c.a, na);
+  const T* b = c.b && (flat || c.kind == CLRSDP_RED_VEC) && c.op != CLRSDP_OP_MAXABS
+                   ? upload_planes<T>(mem, c.b, c.n) : nullptr;
+  const T* da = c.op == CLRSDP_OP_DOTSUM && flat ? upload_planes<T>(mem, c.da, c.n) : nullptr;
+  const T* db = c.op == CLRSDP_OP_DOTSUM && flat ? upload_planes<T>(mem, c.db, c.n) : nullptr;
+  T* out = upload_planes<T>(mem, c.out, nout);
+  T* part = flat ? mem.alloc<T>(RED_G) : nullptr;
+  if (flat && c.part) {
+    const std::vector<double> h = interleave<T>(c.part, RED_G);
+    HIPCHK(hipMemcpy(part, h.data(), RED_G * sizeof(T), hipMemcpyHostToDevice));
+  }
+  StreamOwner so;
+  ScalarParams<T> p{};
+  p.fold_all = 1;
+  switch (c.kind) {
+    case CLRSDP_RED_FLAT_FOLD:  // blk_dot at one rank
+      launch_flat_reduce<T>(so.s, a, b, da, db, c.n, code, part);
+      launch_folds<T>(so.s, out, p, {flat_fold<T>(part, code, 0)}, -1);
+      break;
+    case CLRSDP_RED_FLAT_TREE:  // local_blk_reduce
+      launch_flat_reduce<T>(so.s, a, b, da, db, c.n, code, part);
+      launch_vec_reduce_tree<T>(so.s, part, RED_G, code, out);
+      break;
+    case CLRSDP_RED_VEC:
+      launch_vec_reduce<T>(so.s, a, b, c.n, code, out);
+      break;
+    case CLRSDP_RED_FOLD: {
+      std::vector<FoldRed<T>> pend;
+      for (int64_t q = 0; q < c.nfold; ++q) {
+        const clrsdp_fold& f = c.folds[q];
+        pend.push_back(FoldRed<T>{a + f.off, f.stride, (int)f.cnt, reduce_op_code(c.kind, f.op), (int)q, 0});
+      }
+      launch_folds<T>(so.s, out, p, pend, -1);
+      break;
+    }
+    default:
+      launch_ordered_reduce<T>(so.s, a, (int)c.n, c.stride, code, out);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  download_planes<T>(out, c.out, nout);
+  if (flat && c.part) download_planes<T>(part, c.part, RED_G);
+}
+
+struct SlabCall {
+  int64_t cnt, stride, n;
+  const double *in, *base;
+  double cbase, csum;
+  const double* Q;
+  int64_t ldq;
+  double *out, *out2;
+  int64_t nout, offout;
+};
+
+std::string slab_check(int words, const SlabCall& c) {
+  if (words != 1 && words != 2 && words != 4) return "words must be 1, 2 or 4";
+  if (!c.in || !c.out) return "null argument";
+  if (c.cnt < 1 || c.cnt > 65536) return "cnt must be 1 .. 65536";
+  if (c.n < 1 || c.n > RED_MAX_N) return "n out of range";
+  if (c.stride < c.n || c.stride > RED_MAX_N || c.cnt * c.stride > RED_MAX_N) return "stride out of range";
+  if (c.offout < 0 || c.nout > RED_MAX_N || c.offout + c.n > c.nout) return "the result does not lie inside out";
+  if (c.Q) {
+    if (words != 1) return "slab_qsolve: fp64 only";
+    if (c.n > 128) return "slab_qsolve: n must be 1 .. 128";
+    if (c.ldq < c.n || c.ldq > (1 << 24)) return "slab_qsolve: ldq out of range";
+    if (c.out2) return "slab_qsolve: no second output";
+  }
+  return "";
+}
+
+template <class T>
+void slab_words(int device, const SlabCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  const T* in = upload_planes<T>(mem, c.in, c.cnt * c.stride);
+  const T* base = c.base ? upload_planes<T>(mem, c.base, c.n) : nullptr;
+  T* out = upload_planes<T>(mem, c.out, c.nout);
+  T* out2 = c.out2 ? upload_planes<T>(mem, c.out2, c.nout) : nullptr;
+  const double* Q = nullptr;
+  if constexpr (std::is_same<T, double>::value)
+    if (c.Q) Q = upload_planes<double>(mem, c.Q, c.ldq * c.n);
+  StreamOwner so;
+  if constexpr (std::is_same<T, double>::value) {
+    if (Q)
+      launch_slab_qsolve(so.s, in, (int)c.cnt, c.stride, (int)c.n, base, c.cbase, c.csum, Q,
+                         (int)c.ldq, out + c.offout);
+  }
+  if (!Q)
+    launch_slab_sum4<T>(so.s, in, (int)c.cnt, c.stride, c.n, out + c.offout, base, c.cbase, c.csum,
+                        out2 ? out2 + c.offout : nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  download_planes<T>(out, c.out, c.nout);
+  if (out2) download_planes<T>(out2, c.out2, c.nout);
+}
+
+struct UpdateCall {
+  int64_t nel, nx, ny, ninfo, nblk;
+  double *X, *Y, *x, *y;
+  const double *dX, *dY, *dx, *c, *dy, *b;
+  const int32_t* info;
+  const double *alpha_p, *alpha_d, *eigX, *eigY, *gamma;
+  int pd_feas;
+  double *part, *step;
+};
+
+std::string update_check(int words, const UpdateCall& c) {
+  if (words != 1 && words != 2 && words != 4) return "words must be 1, 2 or 4";
+  if (c.nel < 1 || c.nel > RED_MAX_N) return "nel out of range";
+  if (c.nx < 0 || c.nx > RED_MAX_N) return "nx out of range";
+  if (c.ny < 1 || c.ny > RED_MAX_N) return "ny out of range";
+  if (c.ninfo < 1 || c.ninfo > (1 << 24)) return "ninfo out of range";
+  if (c.nblk < 0 || c.nblk > (1 << 24)) return "nblk out of range";
+  if (!c.X || !c.dX || !c.Y || !c.dY || !c.y || !c.dy || !c.b || !c.info || !c.part) return "null argument";
+  if (c.nx > 0 && (!c.x || !c.dx || !c.c)) return "null argument";
+  if (c.nblk == 0) {
+    if (!c.alpha_p || !c.alpha_d) return "the slot path needs alpha_p and alpha_d";
+    if (c.eigX || c.eigY || c.gamma || c.step) return "the slot path takes no eigenvalues";
+  } else {
+    if (!c.eigX || !c.eigY || !c.gamma || !c.step) return "the fused path needs eigX, eigY, gamma and step";
+    if (c.alpha_p || c.alpha_d) return "the fused path forms alpha itself";
+    if (c.pd_feas != 0 && c.pd_feas != 1) return "pd_feas must be 0 or 1";
+  }
+  return "";
+}
+
+template <class T>
+void update_words(int device, const UpdateCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  T* X = upload_planes<T>(mem, c.X, c.nel);
+  T* Y = upload_planes<T>(mem, c.Y, c.nel);
+  const T* dX = upload_planes<T>(mem, c.dX, c.nel);
+  const T* dY = upload_planes<T>(mem, c.dY, c.nel);
+  T* x = upload_planes<T>(mem, c.x, c.nx);
+  const T* dx = upload_planes<T>(mem, c.dx, c.nx);
+  const T* cv = upload_planes<T>(mem, c.c, c.nx);
+  T* y = upload_planes<T>(mem, c.y, c.ny);
+  const T* dy = upload_planes<T>(mem, c.dy, c.ny);
+  const T* bv = upload_planes<T>(mem, c.b, c.ny);
+  static_assert(sizeof(int) == sizeof(int32_t), "status words are 32-bit");
+  int* info = mem.alloc<int>((size_t)c.ninfo);
+  HIPCHK(hipMemcpy(info, c.info, (size_t)c.ninfo * sizeof(int), hipMemcpyHostToDevice));
+  T* part = upload_planes<T>(mem, c.part, 3 * RED_G);
+  // the four slots of the fused path (mineig_X, mineig_Y, alpha_p, alpha_d), or the two alphas
+  T* sc = c.nblk ? upload_planes<T>(mem, c.step, 4) : mem.alloc<T>(4);
+  StepAlpha<T> sa{};
+  const T *ap = sc + 2, *ad = sc + 3;
+  if (c.nblk) {
+    sa.eigX = upload_planes<T>(mem, c.eigX, c.nblk);
+    sa.eigY = upload_planes<T>(mem, c.eigY, c.nblk);
+    sa.nb = (int)c.nblk;
+    sa.pd_feas = c.pd_feas;
+    sa.gamma = from_limbs<T>(c.gamma);
+    sa.sc = sc;
+    sa.sx = 0;
+    sa.sy = 1;
+    sa.sap = 2;
+    sa.sad = 3;
+    sa.pdslot = 0;  // (read with pd_feas < 0 only)
+  } else {
+    ap = upload_planes<T>(mem, c.alpha_p, 1);
+    ad = upload_planes<T>(mem, c.alpha_d, 1);
+  }
+  StreamOwner so;
+  launch_update_state<T>(so.s, X, dX, Y, dY, c.nel, x, dx, c.nx, cv, y, dy, c.ny, bv, ap, ad, info,
+                         (int)c.ninfo, part, sa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  download_planes<T>(X, c.X, c.nel);
+  download_planes<T>(Y, c.Y, c.nel);
+  download_planes<T>(x, c.x, c.nx);
+  download_planes<T>(y, c.y, c.ny);
+  download_planes<T>(part, c.part, 3 * RED_G);
+  if (c.nblk) download_planes<T>(sc, c.step, 4);
+}
+
 }  // namespace
 
 struct clrsdp_handle {
@@ -4564,6 +4877,54 @@ int32_t clrsdp_gemm_chain(int32_t device, int32_t form, int64_t n, int64_t nprob
     g_last_error = e.what();
     return CLRSDP_E_HIP;
   }
+}
+
+#define WORDS_CALL(fn, ...)                                   \
+  try {                                                       \
+    if (words == 1) fn<double>(__VA_ARGS__);                  \
+    else if (words == 2) fn<mw::dd>(__VA_ARGS__);             \
+    else fn<mw::qd>(__VA_ARGS__);                             \
+    return CLRSDP_OK;                                         \
+  } catch (const ClrsdpError& e) {                            \
+    g_last_error = e.msg;                                     \
+    return e.code;                                            \
+  } catch (const std::exception& e) {                         \
+    g_last_error = e.what();                                  \
+    return CLRSDP_E_HIP;                                      \
+  }
+
+int32_t clrsdp_reduce(int32_t device, int32_t words, int32_t kind, int32_t op, int64_t n,
+                      int64_t stride, const double* a, const double* b, const double* da,
+                      const double* db, int64_t nfold, const clrsdp_fold* folds, double* out,
+                      double* part) {
+  const ReduceCall c{kind, op, n, stride, a, b, da, db, nfold, folds, out, part};
+  const std::string bad = reduce_check(words, c);
+  if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
+  WORDS_CALL(reduce_words, device, c)
+}
+
+int32_t clrsdp_slab_sum(int32_t device, int32_t words, int64_t cnt, int64_t stride, int64_t n,
+                        const double* in, const double* base, double cbase, double csum,
+                        const double* Q, int64_t ldq, double* out, double* out2, int64_t nout,
+                        int64_t offout) {
+  const SlabCall c{cnt, stride, n, in, base, cbase, csum, Q, ldq, out, out2, nout, offout};
+  const std::string bad = slab_check(words, c);
+  if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
+  WORDS_CALL(slab_words, device, c)
+}
+
+int32_t clrsdp_update_state(int32_t device, int32_t words, int64_t nel, double* X, const double* dX,
+                            double* Y, const double* dY, int64_t nx, double* x, const double* dx,
+                            const double* c, int64_t ny, double* y, const double* dy,
+                            const double* b, int64_t ninfo, const int32_t* info,
+                            const double* alpha_p, const double* alpha_d, int64_t nblk,
+                            const double* eigX, const double* eigY, const double* gamma,
+                            int32_t pd_feas, double* part, double* step) {
+  const UpdateCall u{nel, nx, ny, ninfo, nblk, X, Y, x, y, dX, dY, dx, c, dy, b, info,
+                     alpha_p, alpha_d, eigX, eigY, gamma, pd_feas, part, step};
+  const std::string bad = update_check(words, u);
+  if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
+  WORDS_CALL(update_words, device, u)
 }
 
 int32_t clrsdp_set_timing(clrsdp_handle* h, int32_t on) {

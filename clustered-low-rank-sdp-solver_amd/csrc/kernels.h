@@ -938,6 +938,25 @@ __device__ __forceinline__ T madd(T acc, T a, T b) {
   else return acc + a * b;
 }
 
+// The max / min combines of the reductions (flat_reduce, vec_reduce, the folds of scalar_kernel,
+// ordered_reduce, min_fold64): acc = max(acc, v) or min(acc, v), and NaN as soon as the leading
+// limb of either is NaN, whichever position it stands at -- maximum(abs, .) of a residual that
+// holds a NaN is NaN, so no threshold comparison on it is true.  Without a NaN the result is
+// bitwise that of the plain comparison.
+template <class T>
+__device__ __forceinline__ bool lead_nan(const T& v) {
+  const double h = Num<T>::hi(v);
+  return h != h;
+}
+template <class T>
+__device__ __forceinline__ void max_into(T& acc, const T& v) {
+  if (v > acc || lead_nan(v)) acc = v;  // a NaN acc compares false and stays
+}
+template <class T>
+__device__ __forceinline__ void min_into(T& acc, const T& v) {
+  if (v < acc || lead_nan(v)) acc = v;
+}
+
 // flat_reduce's chunk of workgroup `blk` out of `nblk` over [0, n)
 __device__ __forceinline__ void flat_chunk(long long n, int blk, int nblk, long long& lo,
                                            long long& hi) {
@@ -973,12 +992,12 @@ __device__ __forceinline__ T min_fold64(const T* v, int cnt, int lane) {
   for (int i = lane; i < cnt; i += 64) {
     const T e = v[i];
     if (!have) { acc = e; have = true; }
-    else if (e < acc) acc = e;
+    else min_into(acc, e);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const T e = shfl_xor_t(acc, o);
-    if (e < acc) acc = e;
+    min_into(acc, e);
   }
   return acc;
 }
@@ -1103,14 +1122,14 @@ __global__ __launch_bounds__(256) void flat_reduce(const T* __restrict__ a, cons
 #pragma unroll 4
     for (long long e = lo + threadIdx.x; e < hi; e += blockDim.x) {
       const T v = Num<T>::abs_(a[e]);
-      if (v > acc) acc = v;
+      max_into(acc, v);
     }
   }
   red[threadIdx.x] = acc;
   __syncthreads();
   for (int s = blockDim.x / 2; s > 0; s >>= 1) {
     if (threadIdx.x < s) {
-      if (op == 2) { if (red[threadIdx.x + s] > red[threadIdx.x]) red[threadIdx.x] = red[threadIdx.x + s]; }
+      if (op == 2) { T m = red[threadIdx.x]; max_into(m, red[threadIdx.x + s]); red[threadIdx.x] = m; }
       else red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
     }
     __syncthreads();
@@ -3068,7 +3087,7 @@ __global__ __launch_bounds__(vec_reduce_threads<T>()) void vec_reduce(const T* a
   };
   auto comb = [&](T& acc, const T& v) {
     if (op == 2) {
-      if (v > acc) acc = v;
+      max_into(acc, v);
     } else {
       acc += v;
     }
@@ -3097,9 +3116,9 @@ __global__ __launch_bounds__(vec_reduce_threads<T>()) void vec_reduce(const T* a
   T t = a0;
   if constexpr (U == 4) {
     if (op == 2) {
-      if (a1 > t) t = a1;
-      if (a2 > t) t = a2;
-      if (a3 > t) t = a3;
+      max_into(t, a1);
+      max_into(t, a2);
+      max_into(t, a3);
     } else {
       t = (a0 + a1) + (a2 + a3);   // the pairwise order of the round-3 kernel
     }
@@ -3128,8 +3147,8 @@ __global__ void ordered_reduce(const T* in, int cnt, long long stride, int op, T
   for (int i = 1; i < cnt; ++i) {
     const T v = in[(size_t)i * stride];
     if (op == 0) acc += v;
-    else if (op == 2) { if (v > acc) acc = v; }
-    else { if (v < acc) acc = v; }  // op 3: min
+    else if (op == 2) max_into(acc, v);
+    else min_into(acc, v);  // op 3: min
   }
   *out = acc;
 }
@@ -3543,8 +3562,8 @@ __device__ __forceinline__ T fold_wave(const FoldRed<T>& r, int lane) {
     if (r.op == 4) v = Num<T>::abs_(v);
     if (!have) { acc = v; have = true; }
     else if (sum) acc += v;
-    else if (mn) { if (v < acc) acc = v; }
-    else { if (v > acc) acc = v; }
+    else if (mn) min_into(acc, v);
+    else max_into(acc, v);
   }
   // lanes without elements hold the first element (neutral for min/max) or 0 (sum)
   if (!have) {
@@ -3556,8 +3575,8 @@ __device__ __forceinline__ T fold_wave(const FoldRed<T>& r, int lane) {
   for (int o = 32; o > 0; o >>= 1) {
     const T v = shfl_xor_t(acc, o);
     if (sum) acc += v;
-    else if (mn) { if (v < acc) acc = v; }
-    else { if (v > acc) acc = v; }
+    else if (mn) min_into(acc, v);
+    else max_into(acc, v);
   }
   return acc;
 }
@@ -3568,8 +3587,8 @@ __device__ __forceinline__ T fold_wave(const FoldRed<T>& r, int lane) {
 // order, then the same xor butterfly.
 __device__ __forceinline__ double fold_op(int op, double acc, double v) {
   if (op == 0) return acc + v;
-  if (op == 3) return v < acc ? v : acc;
-  return v > acc ? v : acc;
+  if (op == 3) return (v < acc || v != v) ? v : acc;  // min_into / max_into
+  return (v > acc || v != v) ? v : acc;
 }
 __device__ __forceinline__ void fold_all_f64(const ScalarParams<double>& p, double* sc, int lane) {
   double acc[6];

@@ -711,6 +711,146 @@ def gemm_chain(form: str, A1, B1, A2=None, C1=None, a1: float = 1.0, b1: float =
     return [O[p * n * n:(p + 1) * n * n].reshape((n, n), order="F").copy() for p in range(tot)], part
 
 
+_RED_KINDS = {"flat_fold": _lib.RED_FLAT_FOLD, "flat_tree": _lib.RED_FLAT_TREE, "vec": _lib.RED_VEC,
+              "fold": _lib.RED_FOLD, "ordered": _lib.RED_ORDERED}
+_RED_OPS = {"dot": _lib.OP_DOT, "dotsum": _lib.OP_DOTSUM, "sum": _lib.OP_SUM, "max": _lib.OP_MAX,
+            "min": _lib.OP_MIN, "maxabs": _lib.OP_MAXABS}
+
+
+def _limbs2(a, w, what, n=None):
+    """raw limbs (w, n) of a vector as a contiguous float64 array (a 1-D float vector: trailing
+    limbs 0); bits are kept, NaN payloads included"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 1:
+        a = np.concatenate([a[None], np.zeros((w - 1, a.size))])
+    if a.ndim != 2 or a.shape[0] != w or (n is not None and a.shape[1] != n):
+        raise ValueError(f"{what}: raw limbs of shape (words, {'n' if n is None else n}) expected")
+    return np.ascontiguousarray(a)
+
+
+def reduce(kind: str, a, b=None, da=None, db=None, op: str = "dot", stride: int = 1, folds=None,
+           n=None, precision_words: int = 1, device: int = 0, return_partials: bool = False):
+    """One of the solver's scalar reductions on raw limbs (clrsdp_reduce).  ``a`` (and ``b``,
+    ``da``, ``db``) are float arrays of shape (words, n), or 1-D at words 1.  ``kind``:
+    "flat_fold" / "flat_tree" (ops dot, dotsum, maxabs), "vec" (dot, maxabs), "ordered" (min over
+    the ``n`` values ``a[:, i * stride]``) or "fold" with ``folds`` = up to 12 tuples
+    (cnt, stride, off, op) over the arena ``a`` (ops sum, max, min, maxabs).  Returns the limbs of
+    the result, shape (words,) (fold: (words, len(folds))); with ``return_partials`` (flat kinds)
+    also the flat_reduce partials, shape (words, RED_G)."""
+    w = int(precision_words)
+    if kind not in _RED_KINDS:
+        raise ValueError("kind: " + ", ".join(_RED_KINDS))
+    av = _limbs2(a, w, "a")
+    na = av.shape[1]
+    opt = lambda v: None if v is None else _ptr(v)
+    bv, dav, dbv = (None if v is None else _limbs2(v, w, nm, na)
+                    for v, nm in ((b, "b"), (da, "da"), (db, "db")))
+    fl, nfold, nout = None, 0, 1
+    if kind == "fold":
+        if not folds:
+            raise ValueError("fold: a list of (cnt, stride, off, op)")
+        nfold = nout = len(folds)
+        fl = (_lib.Fold * nfold)()
+        for q, (cnt, st, off, o) in enumerate(folds):
+            if o not in _RED_OPS:
+                raise ValueError("op: " + ", ".join(_RED_OPS))
+            fl[q].cnt, fl[q].stride, fl[q].off, fl[q].op = int(cnt), int(st), int(off), _RED_OPS[o]
+        ncall = na
+    else:
+        if op not in _RED_OPS:
+            raise ValueError("op: " + ", ".join(_RED_OPS))
+        ncall = na if kind != "ordered" else (int(n) if n is not None else (na - 1) // int(stride) + 1)
+        if kind == "ordered" and (ncall - 1) * int(stride) + 1 != na:
+            raise ValueError("ordered: a holds (n - 1) * stride + 1 numbers")
+    out = _payload((w, nout)).copy()
+    part = _payload((w, _lib.RED_G)).copy() if return_partials else None
+    _lib.check(_lib.lib().clrsdp_reduce(device, w, _RED_KINDS[kind], _RED_OPS.get(op, -1), ncall,
+                                        int(stride), _ptr(av), opt(bv), opt(dav), opt(dbv), nfold, fl,
+                                        _ptr(out), opt(part)))
+    res = out if kind == "fold" else out[:, 0]
+    return (res, part) if return_partials else res
+
+
+def slab_sum(slabs, n: int, base=None, cbase: float = 0.0, csum: float = 1.0, Q=None, out2: bool = False,
+             guard: int = 0, precision_words: int = 1, device: int = 0):
+    """out[e] = sum_i slabs[i, e] for e < n through slab_sum4, or with ``Q`` (fp64, n x n or ldq x n
+    with ldq > n, column j in ``Q[:, j]``) Q times that sum through slab_qsolve (clrsdp_slab_sum).
+    ``slabs`` has shape (words, cnt, stride) with stride >= n (2-D at words 1); ``base`` (words, n)
+    gives cbase * base + csum * sum.  The outputs carry ``guard`` payload numbers on either side.
+    Returns the raw output arrays, shape (words, n + 2 * guard): out, or (out, out2)."""
+    w = int(precision_words)
+    sl = np.asarray(slabs, dtype=np.float64)
+    if sl.ndim == 2:
+        sl = np.concatenate([sl[None], np.zeros((w - 1,) + sl.shape)])
+    if sl.ndim != 3 or sl.shape[0] != w:
+        raise ValueError("slabs: shape (words, cnt, stride)")
+    cnt, stride = sl.shape[1:]
+    sl = np.ascontiguousarray(sl.reshape(w, cnt * stride))
+    bv = None if base is None else _limbs2(base, w, "base", int(n))
+    qv, ldq = None, 0
+    if Q is not None:
+        Qm = np.asarray(Q, dtype=np.float64)
+        if Qm.ndim != 2 or Qm.shape[1] != n or Qm.shape[0] < n:
+            raise ValueError("Q: ldq x n with ldq >= n")
+        ldq = Qm.shape[0]
+        qv = np.ascontiguousarray(Qm.reshape(-1, order="F"))
+    nout = int(n) + 2 * int(guard)
+    out = _payload((w, nout)).copy()
+    o2 = _payload((w, nout)).copy() if out2 else None
+    _lib.check(_lib.lib().clrsdp_slab_sum(device, w, cnt, stride, int(n), _ptr(sl),
+                                          None if bv is None else _ptr(bv), float(cbase), float(csum),
+                                          None if qv is None else _ptr(qv), ldq, _ptr(out),
+                                          None if o2 is None else _ptr(o2), nout, int(guard)))
+    return (out, o2) if out2 else out
+
+
+def update_state(X, dX, Y, dY, x, dx, c, y, dy, b, info, alpha=None, eig=None, gamma=None,
+                 pd_feas: bool = False, precision_words: int = 1, device: int = 0):
+    """One update_state launch on raw limbs of shape (words, n) (clrsdp_update_state).  ``alpha`` =
+    (alpha_p, alpha_d), ``words`` limbs each: the slot path; or ``eig`` = (eigX, eigY), limbs of
+    shape (words, nblk), with ``gamma`` (``words`` limbs) and ``pd_feas``: the fused path.  ``info``
+    are the status words.  Returns a dict of the raw limbs the launch leaves: X, Y, x, y, part
+    (words, 3, RED_G), and on the fused path step (words, 4) = min eigX, min eigY, alpha_p,
+    alpha_d."""
+    w = int(precision_words)
+    Xv, Yv = (_limbs2(v, w, nm).copy() for v, nm in ((X, "X"), (Y, "Y")))
+    nel = Xv.shape[1]
+    dXv, dYv = _limbs2(dX, w, "dX", nel), _limbs2(dY, w, "dY", nel)
+    xv = _limbs2(x, w, "x").copy()
+    nx = xv.shape[1]
+    dxv, cv = _limbs2(dx, w, "dx", nx), _limbs2(c, w, "c", nx)
+    yv = _limbs2(y, w, "y").copy()
+    ny = yv.shape[1]
+    dyv, bv = _limbs2(dy, w, "dy", ny), _limbs2(b, w, "b", ny)
+    iv = np.ascontiguousarray(info, dtype=np.int32)
+    part = _payload((w, 3 * _lib.RED_G)).copy()
+    lim = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(w))
+    al = eg = gm = step = None
+    nblk = 0
+    if (alpha is None) == (eig is None):
+        raise ValueError("either alpha (the slot path) or eig (the fused path)")
+    if alpha is not None:
+        al = [lim(alpha[0]), lim(alpha[1])]
+    else:
+        eg = [_limbs2(eig[0], w, "eigX"), _limbs2(eig[1], w, "eigY")]
+        nblk = eg[0].shape[1]
+        if eg[1].shape[1] != nblk:
+            raise ValueError("eigX and eigY: one value per block each")
+        gm = lim(gamma)
+        step = _payload((w, 4)).copy()
+    opt = lambda v: None if v is None else _ptr(v)
+    xo = lambda v: _ptr(v) if nx else None
+    _lib.check(_lib.lib().clrsdp_update_state(
+        device, w, nel, _ptr(Xv), _ptr(dXv), _ptr(Yv), _ptr(dYv), nx, xo(xv), xo(dxv), xo(cv), ny,
+        _ptr(yv), _ptr(dyv), _ptr(bv), iv.size, iv.ctypes.data_as(_lib.P_i32),
+        opt(al and al[0]), opt(al and al[1]), nblk, opt(eg and eg[0]), opt(eg and eg[1]), opt(gm),
+        1 if pd_feas else 0, _ptr(part), opt(step)))
+    res = dict(X=Xv, Y=Yv, x=xv, y=yv, part=part.reshape(w, 3, _lib.RED_G))
+    if step is not None:
+        res["step"] = step
+    return res
+
+
 def initial_point(bi: BlockInfo, omega_p, omega_d):
     """x = 0, X = omega_p I, y = 0, Y = omega_d I (MPMP.jl:660-686)."""
     x = np.zeros(sum(bi.dim_S))

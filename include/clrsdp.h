@@ -495,6 +495,94 @@ int32_t clrsdp_gemm_chain(int32_t device, int32_t form, int64_t n, int64_t nprob
                           const double* DdA, const double* DB, double* dot_part, const double* lam,
                           const double* din, double c_agg, double c_in, double* rout);
 
+/* The reductions that steer the loop (mu = <X,Y>/dim, <c,x>, <b,y>, <C,Y>, max |P|, max |p|,
+ * max |d|, min_b lambda_b), each through the launch the solver's stages use: same grid, block
+ * and op mapping.  Numbers are `words` planes (1, 2 or 4; hi limb first); the call runs on a
+ * stream of its own.  `op` is one of CLRSDP_OP_*; a (kind, op) pair that the solver never issues
+ * is CLRSDP_E_ARG.  Every max, min and max-abs is NaN as soon as the leading limb of any element
+ * it covers is NaN, at whatever position.
+ *   CLRSDP_RED_FLAT_FOLD  flat_reduce over a (b, da, db) of n numbers into CLRSDP_RED_G partials,
+ *                         then the fold of the partials inside a scalar_kernel launch (the
+ *                         solver's blk_dot at one rank).  DOT, DOTSUM, MAXABS.
+ *   CLRSDP_RED_FLAT_TREE  flat_reduce, then vec_reduce over the partials (local_blk_reduce:
+ *                         <C,Y>, max |P|, the sharded path).  DOT, DOTSUM, MAXABS.
+ *   CLRSDP_RED_VEC        vec_reduce in one workgroup (<c,x>, <b,y>, max |d|).  DOT, MAXABS.
+ *   CLRSDP_RED_FOLD       nfold (1 .. 12) folds over the arena a of n numbers, fold q over cnt
+ *                         values at a[off + i stride], queued and launched as the solver's
+ *                         pending folds are: scalar_kernel launches of at most six folds each
+ *                         (fp64: fold_all_f64; multi-word: fold_wave).  The call's op and stride
+ *                         are ignored.  out receives nfold numbers.  SUM, MAX, MIN, MAXABS.
+ *   CLRSDP_RED_ORDERED    ordered_reduce of n values at a[i stride] (a holds (n - 1) stride + 1
+ *                         numbers).  MIN.
+ * The FLAT kinds and VEC need stride = 1; b is read by DOT and DOTSUM, da and db by DOTSUM.
+ * out: one number (FOLD: nfold).  part (may be NULL; FLAT kinds only): CLRSDP_RED_G numbers, the
+ * flat_reduce partials.  out and part are copied to the device before the launch and back after.
+ * Refused with CLRSDP_E_ARG before any device work: words, kind or op unknown or not paired, a
+ * NULL a or out or required operand, n outside 1 .. 2^28, a stride other than 1 where none is
+ * taken, folds with another kind, nfold outside 1 .. 12, a fold that leaves the arena, part with a
+ * kind that has no partials. */
+#define CLRSDP_RED_FLAT_FOLD 0
+#define CLRSDP_RED_FLAT_TREE 1
+#define CLRSDP_RED_VEC 2
+#define CLRSDP_RED_FOLD 3
+#define CLRSDP_RED_ORDERED 4
+#define CLRSDP_OP_DOT 0     /* sum a b               */
+#define CLRSDP_OP_DOTSUM 1  /* sum (a + da) (b + db) */
+#define CLRSDP_OP_SUM 2
+#define CLRSDP_OP_MAX 3
+#define CLRSDP_OP_MIN 4
+#define CLRSDP_OP_MAXABS 5
+#define CLRSDP_RED_G 256    /* workgroups, and partials, of flat_reduce and update_state */
+typedef struct {
+  int64_t cnt, stride, off;
+  int32_t op, reserved;
+} clrsdp_fold;
+int32_t clrsdp_reduce(int32_t device, int32_t words, int32_t kind, int32_t op, int64_t n,
+                      int64_t stride, const double* a, const double* b, const double* da,
+                      const double* db, int64_t nfold, const clrsdp_fold* folds, double* out,
+                      double* part);
+
+/* out[offout + e] = sum_{i < cnt} in[i stride + e] for e < n, in slab_sum4's fixed order (the
+ * slabs in four contiguous chunks, eight loads in flight inside each, ((c0 + c1) + (c2 + c3)));
+ * with base (n numbers) cbase base[e] + csum sum (without it cbase and csum are not used), and
+ * the same numbers to out2 when it is given: Q = sum_j slab_j, p = b - sum_j B_j^T x_j,
+ * r = p - sum_j W_j^T t_j.  in holds cnt stride numbers (stride >= n; what lies between n and
+ * stride is never read); out and out2 hold nout numbers, are copied to the device before the
+ * launch and back after it, and the kernel writes offout .. offout + n only.
+ * With Q != NULL (fp64 only, 1 <= n <= 128, out2 NULL) the launch is slab_qsolve: the same r,
+ * then out = Q r with the column-major n x n matrix Q of leading dimension ldq (the explicit
+ * Q^-1 of the block solve); rows n .. ldq of Q are never read.
+ * Refused with CLRSDP_E_ARG before any device work: words other than 1, 2, 4; a NULL in or out;
+ * cnt outside 1 .. 65536; n < 1; stride < n; cnt stride > 2^28; a result outside out; with Q:
+ * words != 1, n > 128, ldq < n, an out2. */
+int32_t clrsdp_slab_sum(int32_t device, int32_t words, int64_t cnt, int64_t stride, int64_t n,
+                        const double* in, const double* base, double cbase, double csum,
+                        const double* Q, int64_t ldq, double* out, double* out2, int64_t nout,
+                        int64_t offout);
+
+/* One update_state launch (the UPDATE stage): X += alpha_p dX, Y += alpha_d dY over nel
+ * elements, x += alpha_p dx over nx (0 allowed: x, dx, c may be NULL), y += alpha_d dy over ny,
+ * all skipped when one of the ninfo status words info[] is nonzero.  part receives
+ * 3 CLRSDP_RED_G numbers: per workgroup the partial <X,Y> of the state the launch leaves
+ * (bitwise flat_reduce's partials of it), then those of <c,x> and of <b,y>.
+ *   nblk = 0  the slot path: alpha_p and alpha_d are `words` limbs each; eigX, eigY, gamma and
+ *             step must be NULL.
+ *   nblk > 0  the fused path of a loop body: eigX and eigY hold nblk eigenvalues, gamma `words`
+ *             limbs, pd_feas 0 or 1; every workgroup forms the two minima and
+ *             alpha = min(1, -gamma / min) (equalised with pd_feas); alpha_p and alpha_d must be
+ *             NULL.  step receives four numbers as workgroup 0 writes them: the minimum of
+ *             eigX, of eigY, alpha_p, alpha_d.
+ * Refused with CLRSDP_E_ARG before any device work: words other than 1, 2, 4; nel < 1, nx < 0,
+ * ny < 1, ninfo < 1, nblk < 0; a NULL required buffer; arguments of the other path; pd_feas
+ * other than 0 or 1 on the fused path. */
+int32_t clrsdp_update_state(int32_t device, int32_t words, int64_t nel, double* X, const double* dX,
+                            double* Y, const double* dY, int64_t nx, double* x, const double* dx,
+                            const double* c, int64_t ny, double* y, const double* dy,
+                            const double* b, int64_t ninfo, const int32_t* info,
+                            const double* alpha_p, const double* alpha_d, int64_t nblk,
+                            const double* eigX, const double* eigY, const double* gamma,
+                            int32_t pd_feas, double* part, double* step);
+
 #ifdef __cplusplus
 }
 #endif
