@@ -797,6 +797,18 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // 16-column panels: n = 127 x 16 blocks 230 -> 155 us (32-column panels: 201 us), while at
   // n <= 64 the one-CU chol_lookahead stays ahead (52 against 73 us; tools/micro/potrf_blk_bench)
   static constexpr int BLK_NB = 16;
+  // CLRSDP_POTRF_BLK is three-state (as CLRSDP_LU_BLK): unset = the above; 0 = no chain at any
+  // word type; explicitly on = the chain replaces potrf_batched at every word type -- fp64 at
+  // every n (potrf64_*, BLK64_NB-column panels, the trailing update on the fp64 matrix cores),
+  // quad-double above 64 (potrf_blk_* in chol_lookahead's LDL form) -- and with it goes
+  // potrf_batched's size bound.  The switch is read when the plan is finalised.
+  // fp64 panel width by measurement (tools/micro/potrf_blk_bench, 2 blocks, us, NB = 16 / 32 /
+  // 64 against potrf_batched): n = 257 258 / 284 / 405 against 1277; n = 640 668 / 708 / 966
+  // against 14180; n = 1262 1540 / 1600 / 2184 against 105903.  A panel costs its serial steps
+  // (diag, the substitution) plus two launches, both growing with NB, while the update's 64 x 64
+  // tiles are already spread over the chip at NB = 16.
+  static constexpr int BLK64_NB = 16;
+  static bool chain_on() { return env_on("CLRSDP_POTRF_BLK"); }
   BlkPotrfDesc<T>* bd = nullptr;
   bool blk = false;
   // potrf_batched: 256 threads, double-double 1024 (see potrf())
@@ -805,9 +817,9 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // whether potrf() factors matrices up to n by potrf_batched (the rest: chol_lookahead or the
   // potrf_blk_* chain, neither with a size bound)
   static bool takes_potrf_batched(int n) {
-    if (std::is_same<T, double>::value) return true;
+    if (std::is_same<T, double>::value) return !chain_on();
     if (std::is_same<T, mw::dd>::value) return n > LA_NMAX && env_off("CLRSDP_POTRF_BLK");
-    return n > LA_NMAX;
+    return n > LA_NMAX && !chain_on();
   }
   // static LDS of potrf_batched (rdg[], fail), from the code object (asked once per word type)
   static size_t pb_lds_static() {
@@ -851,8 +863,16 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       if (!refused.empty() && use == Use::FACTOR) throw ClrsdpError{CLRSDP_E_ARG, refused};
     }
     d = own(h);
-    if constexpr (std::is_same<T, mw::dd>::value) {
-      blk = nmax > 64 && !env_off("CLRSDP_POTRF_BLK");
+    if constexpr (std::is_same<T, double>::value) {
+      blk = use != Use::EIG_ONLY && chain_on();
+      if (blk) {  // (substitution against L_kk: no L_kk^-1 scratch)
+        std::vector<BlkPotrfDesc<T>> b(h.size());
+        for (size_t q = 0; q < h.size(); ++q) b[q] = BlkPotrfDesc<T>{h[q].A, nullptr, h[q].n, h[q].lda};
+        bd = own(b);
+      }
+    } else {
+      if (std::is_same<T, mw::dd>::value) blk = nmax > 64 && !env_off("CLRSDP_POTRF_BLK");
+      else blk = nmax > LA_NMAX && chain_on();
       if (blk) {
         T* li = own(std::vector<T>(h.size() * BLK_NB * BLK_NB, T(0.0)));
         std::vector<BlkPotrfDesc<T>> b(h.size());
@@ -866,17 +886,32 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   void potrf(hipStream_t s, int* info) const {
     if (h.empty()) return;
     if (!refused.empty()) throw ClrsdpError{CLRSDP_E_ARG, refused};
-    if constexpr (std::is_same<T, mw::dd>::value) {
+    if constexpr (std::is_same<T, double>::value) {
       if (blk) {
+        constexpr int NB = BLK64_NB;
+        const unsigned nm = (unsigned)h.size();
+        potrf64_first<NB><<<nm, 256, 0, s>>>(bd, info);
+        for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
+          const int rows = nmax - k0 - NB, nch = cdiv(rows, 64);
+          potrf64_trsm<NB><<<dim3((unsigned)nch, nm), 64, 0, s>>>(bd, k0, info);
+          potrf64_update<NB><<<dim3(1u + (unsigned)(nch * (nch + 1) / 2), nm), 256, 0, s>>>(bd, k0, info);
+        }
+        HIPCHK(hipGetLastError());
+        return;
+      }
+    } else {
+      if (blk) {
+        // (quad-double: the diagonal step in the LDL form of its chol_lookahead instances)
+        constexpr bool LDL = std::is_same<T, mw::qd>::value;
         constexpr int NB = BLK_NB, DT = NB / 16;
         const unsigned nm = (unsigned)h.size();
-        potrf_blk_first<T, false, NB><<<nm, 256, 0, s>>>(bd, info, la_opts());
+        potrf_blk_first<T, LDL, NB><<<nm, 256, 0, s>>>(bd, info, la_opts());
         for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
           const int rows = nmax - k0 - NB, ntr = cdiv(rows, 16);
           int tiles = 0;  // lower 16-tiles of the trailing matrix outside the next diagonal block
           for (int I = DT; I < ntr; ++I) tiles += I + 1;
           potrf_blk_trsm<T, NB><<<dim3((unsigned)ntr, nm), 256, 0, s>>>(bd, k0);
-          potrf_blk_update<T, false, NB><<<dim3(1u + tiles, nm), 256, 0, s>>>(bd, k0, info, la_opts());
+          potrf_blk_update<T, LDL, NB><<<dim3(1u + tiles, nm), 256, 0, s>>>(bd, k0, info, la_opts());
         }
         HIPCHK(hipGetLastError());
         return;

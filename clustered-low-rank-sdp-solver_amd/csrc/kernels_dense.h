@@ -5,6 +5,8 @@
 //                  trailing update.  With chol_inv_tiles (fp64) it replaces spd_inv!
 //                  (MPMP.jl:766), cho! (1846) and the LU solves of S_j / Q (1436-1463, 1501,
 //                  1752-1772): every later solve becomes a GEMM with L^-1.
+//   potrf_blk_*, potrf64_*  the blocked Cholesky chains across workgroups (multi-word / fp64)
+//                  for blocks past the on-chip kernels: diag, trsm and update steps per panel.
 //   eigmin_lds     lambda_min of a symmetric n <= 128 matrix held in LDS: Householder
 //                  tridiagonalisation + Sturm multisection (approx_eig_qr!, MPMP.jl:1857-1870).
 #pragma once
@@ -348,6 +350,16 @@ __global__ __launch_bounds__(64 * (NW + 1)) void chol_lookahead(const MatDesc<T>
 // order from chol_lookahead's column by column: agreement to the multi-word rounding, not bitwise).
 // MPMP.jl:1433-1442 (the factorisation of S_j).
 // ------------------------------------------------------------------------------------------
+// *p where ok, else zero (p is not read then).  The quad-double form names the limbs: the
+// conditional expression on the whole struct went through a 32-byte stack slot there.
+template <class T>
+__device__ __forceinline__ T load_or_zero(bool ok, const T* p) { return ok ? *p : T(0.0); }
+template <>
+__device__ __forceinline__ mw::qd load_or_zero<mw::qd>(bool ok, const mw::qd* p) {
+  double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
+  if (ok) { a = p->x[0]; b = p->x[1]; c = p->x[2]; d = p->x[3]; }
+  return mw::qd(a, b, c, d);
+}
 template <class T>
 struct BlkPotrfDesc {
   T* A;      // the matrix (column-major, lower triangle in, L out, zeros above)
@@ -396,7 +408,7 @@ __global__ __launch_bounds__(256) void potrf_blk_trsm(const BlkPotrfDesc<T>* __r
   }
   for (int e = tid; e < NB * 16; e += 256) {
     const int rr = e % 16, t = e / 16;
-    ar[t][rr] = r0 + rr < b.n ? b.A[r0 + rr + (size_t)(k0 + t) * b.lda] : T(0.0);
+    ar[t][rr] = load_or_zero(r0 + rr < b.n, b.A + r0 + rr + (size_t)(k0 + t) * b.lda);
   }
   __syncthreads();
   const int rr = tid % 16;
@@ -424,8 +436,8 @@ __global__ __launch_bounds__(256) void potrf_blk_update(const BlkPotrfDesc<T>* _
     const int ri = k1 + 16 * I, cj = k1 + 16 * J;
     for (int e = tid; e < NB * 16; e += 256) {
       const int rr = e % 16, t = e / 16;
-      lr[t][rr] = ri + rr < b.n ? b.A[ri + rr + (size_t)(k0 + t) * b.lda] : T(0.0);
-      lc[t][rr] = cj + rr < b.n ? b.A[cj + rr + (size_t)(k0 + t) * b.lda] : T(0.0);
+      lr[t][rr] = load_or_zero(ri + rr < b.n, b.A + ri + rr + (size_t)(k0 + t) * b.lda);
+      lc[t][rr] = load_or_zero(cj + rr < b.n, b.A + cj + rr + (size_t)(k0 + t) * b.lda);
     }
     __syncthreads();
     const int rr = tid % 16, cc = tid / 16, r = ri + rr, c = cj + cc;
@@ -457,6 +469,214 @@ __global__ __launch_bounds__(256) void potrf_blk_update(const BlkPotrfDesc<T>* _
   if (I >= ntr) return;
   J = rem;
   upd_tile(I, J);
+}
+
+// ------------------------------------------------------------------------------------------
+// The fp64 chain (potrf64_*; CLRSDP_POTRF_BLK=1): the same three steps per NB-column panel, with
+//   diag   one wave, lane = row of the NB x NB diagonal block, the row in registers: column j's
+//          pivot and the l_cj of the rank-1 update come by v_readlane (no barrier, no LDS on the
+//          serial chain); writes L_kk and the zeros above its diagonal;
+//   trsm   (64-row chunks x matrices): one row of A_ik per thread, forward substitution against
+//          L_kk in LDS (no explicit inverse, so the factor keeps the plain backward-error bound
+//          of the Cholesky recurrence); chunk 0 zeros the block row right of the panel;
+//   update (lower 64 x 64 tiles of the trailing matrix x matrices): A_ij -= L_ik L_jk^T on
+//          v_mfma_f64_16x16x4f64, four waves of 32 x 32 outputs (2 x 2 MFMA tiles, NB / 4
+//          k-steps each), the two NB-deep operand slabs in LDS at gemm_f64_tile's pitch (64 + 16
+//          doubles: the four k-rows of a fragment read start 32 banks apart).  The product is
+//          formed transposed (the MFMA's A operand is L_jk, negated; B is L_ik), which puts the 16
+//          lanes of an accumulator register on 16 consecutive rows of one column of A: C is
+//          loaded into the accumulators and stored from them in 128-byte runs, with no staging
+//          of the output tile.  Workgroup 0 of each matrix updates the next diagonal block (VALU)
+//          and factors it, the tile workgroups leave that block alone.
+// A failed matrix (info[m] != 0) is left as it is by the launches after the failure.  (Workgroup 0
+// may set info[m] while the tile workgroups of the same launch read it: they then update that
+// matrix or not, and its contents are unspecified either way; no other matrix reads the flag.)
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l),
+                          __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+// one wave: the nb x nb (nb <= NB) block Ds[r + c DP] (lower triangle) -> L at A (ld lda), zeros
+// above the diagonal; the first pivot that is not positive -> info[m] = kbase + its column + 1
+template <int NB>
+__device__ __forceinline__ void potrf64_diag(const double* Ds, int DP, int nb, double* A, int lda,
+                                             int kbase, int* info, int m) {
+  static_assert(NB <= 64, "one lane per row");
+  const int lane = threadIdx.x & 63;
+  double row[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c)
+    row[c] = (lane < nb && c <= lane) ? Ds[lane + c * DP] : (c == lane ? 1.0 : 0.0);
+  int fail = 0;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const double p = readlane_f64(row[j], j);
+    if (!fail && j < nb && !(p > 0.0)) fail = j + 1;
+    if (!fail) {
+      double s, rs;
+      pivot_sqrt(p, s, rs);
+      const double l = lane > j ? row[j] * rs : (lane == j ? s : 0.0);
+      row[j] = l;
+#pragma unroll
+      for (int c = j + 1; c < NB; ++c) row[c] = row[c] - l * readlane_f64(l, c);
+    }
+  }
+  if (fail) {
+    if (lane == 0 && info && info[m] == 0) info[m] = kbase + fail;
+    return;
+  }
+  if (lane < nb) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c)
+      if (c < nb) A[lane + (size_t)c * lda] = c <= lane ? row[c] : 0.0;
+  }
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void potrf64_first(const BlkPotrfDesc<double>* __restrict__ bd,
+                                                     int* __restrict__ info) {
+  constexpr int DP = NB + 1;
+  __shared__ double Ds[NB * DP];
+  const BlkPotrfDesc<double> b = bd[blockIdx.x];
+  const int tid = threadIdx.x, nb = min(NB, b.n);
+  if (tid == 0 && info) info[blockIdx.x] = 0;
+  for (int e = tid; e < NB * NB; e += 256) {
+    const int r = e % NB, c = e / NB;
+    Ds[r + c * DP] = (r < nb && c <= r) ? b.A[r + (size_t)c * b.lda] : 0.0;
+  }
+  __syncthreads();
+  if (tid < 64) potrf64_diag<NB>(Ds, DP, nb, b.A, b.lda, 0, info, blockIdx.x);
+}
+
+// trsm of panel k: blockIdx.y = matrix, blockIdx.x = 64-row chunk of rows k0 + NB .. n-1
+template <int NB>
+__global__ __launch_bounds__(64) void potrf64_trsm(const BlkPotrfDesc<double>* __restrict__ bd,
+                                                   int k0, const int* __restrict__ info) {
+  const BlkPotrfDesc<double> b = bd[blockIdx.y];
+  const int k1 = k0 + NB, tid = threadIdx.x;
+  if (k1 >= b.n) return;
+  if (info && info[blockIdx.y]) return;
+  if (blockIdx.x == 0)
+    for (int e = tid; e < NB * (b.n - k1); e += 64) {
+      const int r = k0 + e % NB, c = k1 + e / NB;
+      b.A[r + (size_t)c * b.lda] = 0.0;
+    }
+  if (64 * (int)blockIdx.x >= b.n - k1) return;
+  __shared__ double Ls[NB * NB];  // L_kk, [q + p NB]
+  __shared__ double rd[NB];       // 1 / l_qq
+  for (int e = tid; e < NB * NB; e += 64) {
+    const int q = e % NB, p = e / NB;
+    Ls[e] = q >= p ? b.A[(k0 + q) + (size_t)(k0 + p) * b.lda] : 0.0;
+  }
+  if (tid < NB) rd[tid] = 1.0 / b.A[(k0 + tid) + (size_t)(k0 + tid) * b.lda];
+  __syncthreads();
+  const int r = k1 + 64 * blockIdx.x + tid;
+  if (r >= b.n) return;
+  // (row[] in registers: every index is static, as in potrf_batched's panel)
+  double row[NB];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    double x = b.A[r + (size_t)(k0 + q) * b.lda];
+#pragma unroll
+    for (int p = 0; p < q; ++p) x = x - row[p] * Ls[q + p * NB];
+    x = x * rd[q];
+    row[q] = x;
+    b.A[r + (size_t)(k0 + q) * b.lda] = x;
+  }
+}
+
+// update of panel k fused with the diagonal step of panel k+1: blockIdx.y = matrix, blockIdx.x =
+// 0 the next diagonal block, 1 + q the lower 64 x 64 tile q = I (I + 1) / 2 + J of the trailing
+// matrix (rows / columns k1 = k0 + NB .. n-1)
+template <int NB>
+__global__ __launch_bounds__(256) void potrf64_update(const BlkPotrfDesc<double>* __restrict__ bd,
+                                                      int k0, int* __restrict__ info) {
+  constexpr int LM = 64 + 16, SZ = NB * LM, DP = NB + 1;
+  static_assert(2 * NB * DP <= 2 * SZ && NB % 4 == 0, "LDS image");
+  __shared__ double sm[2 * SZ];
+  const BlkPotrfDesc<double> b = bd[blockIdx.y];
+  const int k1 = k0 + NB, tid = threadIdx.x, n = b.n, lda = b.lda;
+  if (k1 >= n) return;
+  if (info && info[blockIdx.y]) return;
+  double* A = b.A;
+  if (blockIdx.x == 0) {
+    const int nb = min(NB, n - k1);
+    double* Ps = sm;            // rows k1 .. of panel k: Ps[r + t DP]
+    double* Ds = sm + NB * DP;  // the updated diagonal block
+    for (int e = tid; e < NB * NB; e += 256) {
+      const int r = e % NB, t = e / NB;
+      Ps[r + t * DP] = r < nb ? A[(k1 + r) + (size_t)(k0 + t) * lda] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += 256) {
+      const int r = e % NB, c = e / NB;
+      double v = 0.0;
+      if (r < nb && c <= r) {
+        v = A[(k1 + r) + (size_t)(k1 + c) * lda];
+#pragma unroll 8
+        for (int t = 0; t < NB; ++t) v = v - Ps[r + t * DP] * Ps[c + t * DP];
+      }
+      Ds[r + c * DP] = v;
+    }
+    __syncthreads();
+    if (tid < 64) potrf64_diag<NB>(Ds, DP, nb, A + k1 + (size_t)k1 * lda, lda, k1, info, blockIdx.y);
+    return;
+  }
+  const int q = blockIdx.x - 1;
+  int I = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
+  while ((I + 1) * (I + 2) / 2 <= q) ++I;
+  while (I * (I + 1) / 2 > q) --I;
+  const int J = q - I * (I + 1) / 2;
+  if (64 * I >= n - k1) return;
+  const int i0 = k1 + 64 * I, j0 = k1 + 64 * J;
+  double* Ri = sm;       // L_ik: element (row, t) at [t LM + row]
+  double* Rj = sm + SZ;  // L_jk
+  {
+    const int i = tid & 63;
+    const size_t gi = (size_t)min(i0 + i, n - 1), gj = (size_t)min(j0 + i, n - 1);
+#pragma unroll
+    for (int u = 0; u < NB / 4; ++u) {
+      const int t = (tid >> 6) + 4 * u;
+      Ri[t * LM + i] = gload(A + gi + (size_t)(k0 + t) * lda);
+      Rj[t * LM + i] = gload(A + gj + (size_t)(k0 + t) * lda);
+    }
+  }
+  const int lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1, lr = lane & 15, lk = lane >> 4;
+  // accumulator register r of (mj, ni): row i0 + 32 wm + 16 ni + lr, column j0 + 32 wn + 16 mj + lk + 4 r
+  d4 acc[2][2];
+#pragma unroll
+  for (int mj = 0; mj < 2; ++mj)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = i0 + 32 * wm + 16 * ni + lr, c = j0 + 32 * wn + 16 * mj + lk + 4 * r;
+        acc[mj][ni][r] = (rr < n && rr >= c) ? gload(A + rr + (size_t)c * lda) : 0.0;
+      }
+  __syncthreads();
+#pragma unroll
+  for (int kk = 0; kk < NB; kk += 4) {
+    double af[2], bf[2];
+#pragma unroll
+    for (int mj = 0; mj < 2; ++mj) af[mj] = -Rj[(kk + lk) * LM + 32 * wn + 16 * mj + lr];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) bf[ni] = Ri[(kk + lk) * LM + 32 * wm + 16 * ni + lr];
+#pragma unroll
+    for (int mj = 0; mj < 2; ++mj)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+        acc[mj][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mj], bf[ni], acc[mj][ni], 0, 0, 0);
+  }
+#pragma unroll
+  for (int mj = 0; mj < 2; ++mj)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = i0 + 32 * wm + 16 * ni + lr, c = j0 + 32 * wn + 16 * mj + lk + 4 * r;
+        // (rr >= c: c < n; rows below k1 + NB with columns up to them are the next diagonal block)
+        if (rr < n && rr >= c && rr >= k1 + NB) A[rr + (size_t)c * lda] = acc[mj][ni][r];
+      }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -388,7 +388,11 @@ def potrf(blocks, inverse: bool = False, precision_words: int = 1, device: int =
     """Cholesky factor ``A = L L^T`` of each symmetric positive definite block at fp64 /
     double-double / quad-double (clrsdp_potrf: cho!, as the solver's potrf plan runs it), or with
     ``inverse`` its inverse ``L^-1`` (the on-chip factorisation with the inverse: n <= 256 at
-    fp64, n <= 64 at multi-word).  Blocks are float arrays, object arrays of mpmath numbers (split
+    fp64, n <= 64 at multi-word).  Without ``inverse`` the one-CU ``potrf_batched`` factors fp64
+    blocks and quad-double blocks above 64, and refuses n > 1262 / n > 302 (``CLRSDP_E_ARG``);
+    ``CLRSDP_POTRF_BLK`` is three-state: unset or ``0`` that default with its refusals, explicitly
+    on (``=1``) a blocked chain across workgroups in its place (fp64 at every n, quad-double above
+    64, double-double as by default) with no size bound up to 4096.  Blocks are float arrays, object arrays of mpmath numbers (split
     exactly into limbs) or raw limbs of shape (words, n, n); only their lower triangles are used.
     Returns ``(L, info)``: per block the lower triangle of the result (``np.tril``: floats at
     words 1, else the exact limb sums as mpmath numbers) and ``info`` = 0 or the 1-based column of

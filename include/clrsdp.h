@@ -353,6 +353,13 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
  *     past the n at which it fits (fp64 1262, quad-double 302, double-double 622) the call is
  *     CLRSDP_E_ARG, as the loop body's Cholesky of such a block is (clrsdp_iterate,
  *     clrsdp_run_stage; with CLRSDP_FACT_LU_SQ the body factors it by pivoted LU instead).
+ *     CLRSDP_POTRF_BLK is three-state: unset and 0 as above (the default and its refusals are
+ *     unchanged); set to anything that does not start with 0, a blocked chain across workgroups
+ *     replaces potrf_batched at every word type -- fp64: potrf64_first / _trsm / _update at
+ *     every n (16-column panels, the panel by substitution, the trailing update on the fp64
+ *     matrix cores; zeros above the diagonal); quad-double: chol_lookahead up to 64, the
+ *     potrf_blk_* chain (LDL diagonal step) beyond; double-double as above -- and then no
+ *     Cholesky is refused for its size, here (n up to 4096) or in a handle's FACTOR stage.
  *   inverse = 1: A receives L_b^-1 (chol_inv_tiles at fp64, n[b] <= 256; chol_lookahead with
  *     the inverse at double-double and quad-double, n[b] <= 64; larger: CLRSDP_E_ARG).  The
  *     lower triangle holds L_b^-1 and the strict upper triangle exact zeros, every entry written

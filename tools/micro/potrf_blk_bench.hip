@@ -4,6 +4,8 @@
 // the L entries relative to max |L| of the block, and the failure flags.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 potrf_blk_bench.hip -o ../../microbin/potrf_blk_bench
 //   microbin/potrf_blk_bench n batch
+// Every run also times the fp64 chain (potrf64_*, NB = 16 / 32 / 64) and, for 64 < n <= 512, the
+// quad-double chain against potrf_batched (the numbers behind MatPlan's BLK64_NB).
 // With -DCLRSDP_LA_TRACE (binary potrf_blk_trace): chol_lookahead's per-column timestamps
 // (shader clock) of the chain wave and one bulk wave, averaged over the columns and blocks.
 #include <hip/hip_runtime.h>
@@ -130,6 +132,98 @@ void run(const char* name, int n, int nmat) {
          name, LDL ? " LDL" : "", n, nmat, tr, t32, e32, t16, e16, upper_bad, bad[0], bad[1], bad[2]);
 }
 
+// ---- the fp64 chain (potrf64_*) and the quad-double chain (potrf_blk_* in the LDL form) against
+// potrf_batched: n up to potrf_batched's bound (1262 fp64 / 302 quad-double) for the comparison,
+// beyond it the chain alone
+template <int NB>
+void blocked64(const BlkPotrfDesc<double>* bd, int nmat, int n, int* info, hipStream_t s) {
+  potrf64_first<NB><<<nmat, 256, 0, s>>>(bd, info);
+  for (int k0 = 0; k0 + NB < n; k0 += NB) {
+    const int nch = (n - k0 - NB + 63) / 64;
+    potrf64_trsm<NB><<<dim3(nch, nmat), 64, 0, s>>>(bd, k0, info);
+    potrf64_update<NB><<<dim3(1 + nch * (nch + 1) / 2, nmat), 256, 0, s>>>(bd, k0, info);
+  }
+}
+
+template <class T>
+void run_vs_batched(const char* name, int n, int nmat) {
+  constexpr bool F64 = std::is_same<T, double>::value;
+  const size_t nn = (size_t)n * n;
+  std::vector<T> h(nn * nmat);
+  srand(7);
+  {  // A = B B^T / n + I with B n x 32 (cheap to build at n ~ 1000), the same for every block
+    std::vector<double> B((size_t)n * 32);
+    for (auto& v : B) v = (double)rand() / RAND_MAX - 0.5;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        double s = i == j ? 1.0 : 0.0;
+        for (int k = 0; k < 32; ++k) s += B[i + (size_t)k * n] * B[j + (size_t)k * n] / n;
+        for (int b = 0; b < nmat; ++b) h[b * nn + i + (size_t)j * n] = T(s);
+      }
+  }
+  T *dA, *dW, *dLi;
+  CK(hipMalloc(&dA, h.size() * sizeof(T)));
+  CK(hipMalloc(&dW, h.size() * sizeof(T)));
+  CK(hipMalloc(&dLi, (size_t)nmat * 16 * 16 * sizeof(T)));
+  CK(hipMemcpy(dA, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  std::vector<MatDesc<T>> md(nmat);
+  std::vector<BlkPotrfDesc<T>> bdh(nmat);
+  for (int b = 0; b < nmat; ++b) {
+    md[b] = {dW + b * nn, n, n};
+    bdh[b] = {dW + b * nn, dLi + (size_t)b * 16 * 16, n, n};
+  }
+  MatDesc<T>* dmd;
+  BlkPotrfDesc<T>* dbd;
+  CK(hipMalloc(&dmd, nmat * sizeof(MatDesc<T>)));
+  CK(hipMalloc(&dbd, nmat * sizeof(BlkPotrfDesc<T>)));
+  CK(hipMemcpy(dmd, md.data(), nmat * sizeof(MatDesc<T>), hipMemcpyHostToDevice));
+  CK(hipMemcpy(dbd, bdh.data(), nmat * sizeof(BlkPotrfDesc<T>), hipMemcpyHostToDevice));
+  int* info;
+  CK(hipMalloc(&info, nmat * sizeof(int)));
+  auto prep = [&] { CK(hipMemcpy(dW, dA, h.size() * sizeof(T), hipMemcpyDeviceToDevice)); };
+  std::vector<T> ref(h.size()), w(h.size());
+  const size_t lds = sizeof(T) * (16 * 16 + (size_t)16 * n);
+  const bool fits = lds + 16 * sizeof(T) + 16 <= 160 * 1024;
+  float tb = 0.f;
+  if (fits) {
+    tb = timeit(prep, [&] { potrf_batched<T, 16, 256><<<nmat, 256, lds>>>(dmd, info); });
+    CK(hipMemcpy(ref.data(), dW, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+  }
+  auto diff = [&]() {  // the largest |difference| of the lower triangle relative to max |L|
+    CK(hipMemcpy(w.data(), dW, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+    std::vector<int> hi(nmat);
+    CK(hipMemcpy(hi.data(), info, nmat * sizeof(int), hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int b = 0; b < nmat; ++b) bad += hi[b] != 0;
+    double e = 0.0, mx = 0.0;
+    if (fits)
+      for (int c = 0; c < n; ++c)
+        for (int r = c; r < n; ++r) {
+          const size_t i = r + (size_t)c * n;
+          mx = fmax(mx, fabs(Num<T>::hi(ref[i])));
+          e = fmax(e, fabs(Num<T>::hi(w[i] - ref[i])));
+        }
+    printf(" (diff %.1e, info!=0 %d)", fits ? e / mx : -1.0, bad);
+  };
+  printf("%s n=%d batch=%d: potrf_batched %.1f us |", name, n, nmat, tb);
+  if constexpr (F64) {
+    const float t16 = timeit(prep, [&] { blocked64<16>(dbd, nmat, n, info, 0); });
+    printf(" chain NB=16 %.1f us", t16);
+    diff();
+    const float t32 = timeit(prep, [&] { blocked64<32>(dbd, nmat, n, info, 0); });
+    printf(" | NB=32 %.1f us", t32);
+    diff();
+    const float t64 = timeit(prep, [&] { blocked64<64>(dbd, nmat, n, info, 0); });
+    printf(" | NB=64 %.1f us", t64);
+    diff();
+  } else {
+    const float t16 = timeit(prep, [&] { blocked<T, true, 16>(dbd, nmat, n, info, 0); });
+    printf(" chain LDL NB=16 %.1f us", t16);
+    diff();
+  }
+  printf("\n");
+}
+
 #ifdef CLRSDP_LA_TRACE
 template <class T, bool INV, bool LDL, int NMAX, int NW, bool SKIP0 = false>
 void trace_run(const char* name, int n, int nmat) {
@@ -214,6 +308,8 @@ int main(int argc, char** argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 127, nmat = argc > 2 ? atoi(argv[2]) : 16;
   if (n <= 128) run<dd, false>("dd", n, nmat);
   if (n <= 64) run<qd, true>("qd", n, nmat);
+  run_vs_batched<double>("fp64", n, nmat);
+  if (n > 64 && n <= 512) run_vs_batched<qd>("qd", n, nmat);
   return 0;
 }
 #endif
