@@ -40,7 +40,7 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_restore_state", "clrsdp_step_length", "clrsdp_set_factorization",
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
            "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
-           "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state"]
+           "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info"]
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -108,6 +108,12 @@ class Fold(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SchurInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fast", "fused", "one", "d64", "grp2", "fused_y", "n_fwg",
+                                         "n_ptiles", "n_gsum", "ozaki", "pair_upper", "full",
+                                         "s_lower")]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p)
 
 _lib = None
@@ -153,6 +159,7 @@ def lib():
     L.clrsdp_get_factorization.argtypes = [C.c_void_p, P_i32]
     L.clrsdp_set_graph.argtypes = [C.c_void_p, C.c_int32]
     L.clrsdp_comm_info.argtypes = [C.c_void_p, P_i32, P_i32]
+    L.clrsdp_schur_info.argtypes = [C.c_void_p, C.POINTER(SchurInfo)]
     L.clrsdp_eigmin.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_f64]
     L.clrsdp_getrf.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32, P_i32]
     L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]

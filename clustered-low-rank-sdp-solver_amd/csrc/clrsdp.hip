@@ -1244,6 +1244,7 @@ struct HandleBase {
   virtual int get_factorization() const = 0;
   virtual void set_graph(int on) = 0;
   virtual void comm_info(int* nranks, int* backend) const = 0;
+  virtual void schur_info(struct clrsdp_schur_info* out) const = 0;
 };
 
 template <class T>
@@ -1274,6 +1275,7 @@ struct Solver final : HandleBase {
   // products), else 128
   const int s_single = (std::is_same<T, double>::value && env_on("CLRSDP_CHOL256")) ? 256 : 128;
   bool s_lower = false;  // the last SCHUR enqueued assembled the lower triangle of S only
+  int schur_full = -1;   // the `full` of the last SCHUR enqueued (-1: none yet), for schur_info
 
   // ---------------- device memory
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -2401,6 +2403,22 @@ struct Solver final : HandleBase {
     fact_flags = flags;
   }
   int get_factorization() const override { return fact_flags; }
+  // what build_fast_schur / build_ozaki / upload decided, and the last SCHUR's store form
+  void schur_info(struct clrsdp_schur_info* o) const override {
+    o->fast = fast_schur;
+    o->fused = schur_fused;
+    o->one = schur_fused && fused_one;
+    o->d64 = schur_fused && fused_d64;
+    o->grp2 = schur_fused ? fused_grp2 : any_grp2;
+    o->fused_y = schur_fused && fused_y;
+    o->n_fwg = schur_fused ? n_fwg : 0;
+    o->n_ptiles = n_ptiles;
+    o->n_gsum = n_gsum;
+    o->ozaki = use_oz;
+    o->pair_upper = mw_pair_upper;
+    o->full = schur_full;
+    o->s_lower = schur_full < 0 ? -1 : (s_lower ? 1 : 0);
+  }
 
   // ---------------- host <-> device conversion
   void put(T* dst, const double* planes, int64_t nplane, int64_t first, int64_t count) {
@@ -2753,6 +2771,7 @@ struct Solver final : HandleBase {
         // pivoted LU and the rank-group sums read all of it
         const bool full = !fac2 || n_gsum > 0 || lu_sq();
         s_lower = schur_fused && !full;
+        schur_full = (full || !schur_fused) ? 1 : 0;  // (schur_pairs_f64 always stores both triangles)
         if (schur_fused && fused_d64 && fused_grp2)
           schur_fused_f64<0, true, true, true, true><<<n_fwg, 512, schur_fused::LDS, stream>>>(d_fpd, d_fpt2d, stamps + 4, full);
         else if (schur_fused && fused_d64)
@@ -2779,6 +2798,7 @@ struct Solver final : HandleBase {
         return;
       }
     }
+    schur_full = 1;  // schur_assemble writes both triangles
     if (use_oz) {
       launch_ozaki();
     } else {
@@ -4978,6 +4998,12 @@ int32_t clrsdp_comm_info(const clrsdp_handle* h, int32_t* nranks, int32_t* backe
   h->impl->comm_info(&n, &b);
   *nranks = n;
   *backend = b;
+  return CLRSDP_OK;
+}
+
+int32_t clrsdp_schur_info(const clrsdp_handle* h, struct clrsdp_schur_info* out) {
+  if (!h || !out) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+  h->impl->schur_info(out);
   return CLRSDP_OK;
 }
 

@@ -259,6 +259,14 @@ class DeviceSolver:
         self.check(self.L.clrsdp_comm_info(self.h, C.byref(n), C.byref(b)))
         return n.value, {0: "none", 1: "rccl", 2: "callback"}.get(b.value, str(b.value))
 
+    def schur_info(self) -> dict:
+        """clrsdp_schur_info: what this handle's SCHUR stage launches, as a dict of ints -- fast,
+        fused, one, d64, grp2, fused_y, n_fwg, n_ptiles, n_gsum, ozaki, pair_upper, and full /
+        s_lower of the last SCHUR enqueued (-1 before any).  Read-only."""
+        o = _lib.SchurInfo()
+        self.check(self.L.clrsdp_schur_info(self.h, C.byref(o)))
+        return {n: int(getattr(o, n)) for n, _ in _lib.SchurInfo._fields_}
+
     def set_stream(self, stream_ptr: int):
         self.check(self.L.clrsdp_set_stream(self.h, C.c_void_p(stream_ptr)))
 

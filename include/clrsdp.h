@@ -292,6 +292,37 @@ int32_t clrsdp_set_graph(clrsdp_handle* h, int32_t on);
  * reference (shared-memory threads, MPMP.jl:1486-1494, 1758-1761). */
 int32_t clrsdp_comm_info(const clrsdp_handle* h, int32_t* nranks, int32_t* backend);
 
+/* What this handle's SCHUR stage launches (read-only; adds no switch and no launch).  The plan is
+ * fixed by clrsdp_create / clrsdp_upload_constraints from the block shapes, the ranks and the
+ * CLRSDP_SCHUR_* / CLRSDP_OZAKI / CLRSDP_MW_PAIR_UPPER environment at that time:
+ *   fast        fp64 and every local block m = 1: the V^T X^-1 / V^T Y products and the pairing
+ *               kernels below (0: the general path, four GEMMs or the int8 products, extract_AY
+ *               and schur_assemble)
+ *   fused       schur_fused_f64 runs (0 with fast: the V^T X^-1 GEMM + schur_pairs_f64)
+ *   one, d64    its one-column-tile-per-workgroup form, and that form's delta <= 64 instance
+ *   grp2        fused: the rank-2 group-sum epilogue instance; unfused: some cluster has its
+ *               2 x 2 groups summed by schur_pairs_f64 (per descriptor)
+ *   fused_y     V^T Y formed on chip by the fused kernel (0: read from the GEMM's output)
+ *   n_fwg       workgroups of the fused launch (0 when it does not run)
+ *   n_ptiles    workgroups of schur_pairs_f64, were it to run (fast only)
+ *   n_gsum      clusters summed from the G arena by schur_gsum (L > 1 or mixed ranks)
+ *   ozaki       the int8 (oz_split / oz_gemm) products (double-double, every block m = 1)
+ *   pair_upper  multi-word, every m = 1: BX / BY hold their upper 16-tiles only
+ *   full        of the last SCHUR enqueued: 1 = both triangles of every S_j were stored by the
+ *               kernels (always so without the fused kernel: schur_pairs_f64, schur_gsum and
+ *               schur_assemble store both), 0 = the fused kernel was told to store the lower
+ *               one; -1 before any
+ *   s_lower     BUF_S holds the lower triangle only (clrsdp_get_buffer mirrors it on the host);
+ *               0 again once FACTOR has overwritten S; -1 before any SCHUR
+ * No reference counterpart (compute_S_integrated, MPMP.jl:1373-1398, is one loop nest). */
+struct clrsdp_schur_info {  /* (a tag only: the function below has the same name) */
+  int32_t fast, fused, one, d64, grp2, fused_y;
+  int32_t n_fwg, n_ptiles, n_gsum;
+  int32_t ozaki, pair_upper;
+  int32_t full, s_lower;
+};
+int32_t clrsdp_schur_info(const clrsdp_handle* h, struct clrsdp_schur_info* out);
+
 /* Factorisations of S_j, Q and X (flags, default CLRSDP_FACT_FALLBACK).  The device factorises
  * S_j and Q by Cholesky (they are SPD) and X^-1 by the Cholesky inverse (spd_inv!).  The
  * reference factorises S_j and Q by partially pivoted LU (approx_lu!, MPMP.jl:1433-1442,

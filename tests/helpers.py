@@ -305,13 +305,14 @@ def _ld_gemm_nt(A, Bt, threads=8):
     return out
 
 
-def schur_dense(cons, bi, X_inv, Y):
+def schur_dense(cons, bi, X_inv, Y, dtype=np.longdouble):
     """Dense restatement of the SCHUR stage (the 4-term formula, MPMP.jl:1373-1398, as
     oracle/mpmp_oracle.py:compute_S_integrated assembles it): V, X^-1 and Y taken as float64, every
     product and sum accumulated in np.longdouble, all of it as GEMMs, Hadamard products and group
     sums -- usable at K of several thousand, where the oracle's per-entry code is not.
-    Returns (S, A_Y) as flat longdouble arrays in the layout of BUF_S and BUF_AY."""
-    ld = np.longdouble
+    Returns (S, A_Y) as flat longdouble arrays in the layout of BUF_S and BUF_AY.  ``dtype``
+    np.float64 gives the plain float64 restatement of the same formula (tests/schur_cases.py)."""
+    ld = dtype
     S_out, AY_out = [], []
     for j in range(bi.J):
         m, N, D = bi.m[j], bi.n_samples[j], bi.dim_S[j]

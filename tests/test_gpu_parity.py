@@ -178,7 +178,11 @@ def test_schur_fused_matches_unfused(pk, monkeypatch):
     """schur_fused_f64 against the unfused kernels on the C3 cluster shape (K = 255: four row
     blocks, the last one ragged, and the wrapped tile assignment), on rank-2 blocks (G into the
     BX arena, then schur_gsum) and on K = 40 (one row block): S and A_Y agree to fp64 round-off,
-    and every S_j the kernel writes directly (rank-1 samples) is exactly symmetric."""
+    and every S_j the kernel writes directly (rank-1 samples) is exactly symmetric.
+    (With the default flags and every dim_S <= 256 the fused kernel stores the lower triangle only
+    -- schur_info()["s_lower"] -- and the buffer read here is mirrored on the host, so that
+    symmetry holds by construction; the kernel's own two triangles are compared in the FACT_LU_SQ
+    runs of tests/test_gpu_schur.py::test_schur_fp64_dispatch_rows.)"""
     from clrsdp_amd import _lib as L
     P = pk.make_params("0.3", "0.1", "0.7", 0)
     for cfg in (dict(J=3, delta=128, rank=1, n_y=20), dict(J=2, delta=64, rank=2, n_y=16),
@@ -243,7 +247,11 @@ def test_schur_stage_beyond_64_row_blocks(pk, monkeypatch, delta, rank, N, env):
     A_Y was never written, and no error raised).  S and A_Y against the dense longdouble
     restatement of the 4-term formula at the fp64 tolerance; the S_j the kernel writes directly
     (rank 1) is exactly symmetric.  K = 4096 is the last size the old encoding covered; the
-    multi-tile form and the unfused pair are pinned at the same K."""
+    multi-tile form and the unfused pair are pinned at the same K.
+    (dim_S > 256 here, so the kernel stores both triangles -- full = 1 -- and the symmetry
+    assertion does compare its (p, q) and mirror writes at this size; at dim_S <= 256 with the
+    default flags it would hold by the host's mirroring, and the small shapes are covered by the
+    FACT_LU_SQ runs of tests/test_gpu_schur.py::test_schur_fp64_dispatch_rows.)"""
     from clrsdp_amd import _lib as L
     for k in ("CLRSDP_SCHUR_FUSED", "CLRSDP_SCHUR_FUSED_ONE", "CLRSDP_SCHUR_FUSED_D64", "CLRSDP_SCHUR_GRP2"):
         monkeypatch.delenv(k, raising=False)  # (the library's own choice of path unless env says so)
