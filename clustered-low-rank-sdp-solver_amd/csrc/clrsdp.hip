@@ -882,6 +882,78 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       }
     }
     if (!std::is_same<T, double>::value) redo = own(std::vector<int>(h.size(), 1));
+    eig_blk = use == Use::EIG_ONLY && env_on("CLRSDP_EIG_BLK");
+    if (eig_dispatch(nmax, eig_blk) == CLRSDP_EIG_K_BLK) finalize_eig_chain();
+  }
+  // ---- lambda_min of blocks past the LDS kernels across workgroups (eigblk_*, kernels_dense.h)
+  // CLRSDP_EIG_BLK=1: a batch that eigmin() would give to the one-CU eigmin_batched goes to the
+  // chain instead -- one launch per column over strips of EIG_R rows, then eigblk_sturm.  Read
+  // when the plan is finalised (a captured body cannot change route).  Opt-in: the measurements
+  // and the crossover against eigmin_batched are in DESIGN.md §1.
+  // EIG_R: one thread per row and one wave per strip, so the strip height only decides how
+  // many waves share the rows (tools/micro/eig_blk_bench)
+  static constexpr int EIG_R = 64;
+  bool eig_blk = false;
+  bool eig_tri = true;  // eigblk_sturm keeps the tridiagonal in LDS
+  EigBlkDesc<T>* ed = nullptr;
+  // the largest n whose v_k and w (eigblk_col's dynamic LDS) fit one CU
+  static constexpr int eig_chain_nmax() { return (int)(LDS_MAX / (2 * sizeof(T))); }
+  // The kernel eigmin() launches for a batch whose largest block is nmax (CLRSDP_EIG_K_*,
+  // clrsdp.h), `chain` being CLRSDP_EIG_BLK as the plan read it
+  static int eig_dispatch(int nmax, bool chain) {
+    if (std::is_same<T, double>::value && nmax <= 128) return CLRSDP_EIG_K_SPLIT;  // matrix in registers
+    if (!std::is_same<T, double>::value) {
+      // n <= 64: an fp64 eigenpair refined at the word's width (eigmin_mx; the blocks it cannot
+      // certify go to eigmin_lds2 in a second, flagged launch) unless CLRSDP_EIG_MX=0
+      static const bool mx = !env_off("CLRSDP_EIG_MX");
+      if (mx && nmax <= 64 && eigmx_lds_bytes<T>(nmax) + EIGMX_STATIC_LDS <= LDS_MAX &&
+          eig2_lds_bytes<T>(nmax) <= LDS_MAX)
+        return CLRSDP_EIG_K_MX;
+      // eigmin_lds2 (two barriers per column) where its column slots fit (qd: 8 column slots
+      // per lane, n <= 64)
+      if (eig2_lds_bytes<T>(nmax) <= LDS_MAX && (sizeof(T) <= 16 || nmax <= 64)) return CLRSDP_EIG_K_LDS2;
+    }
+    if (eig_lds_bytes<T>(nmax) <= LDS_MAX) return CLRSDP_EIG_K_LDS;
+    return chain ? CLRSDP_EIG_K_BLK : CLRSDP_EIG_K_BATCHED;
+  }
+  void finalize_eig_chain() {
+    if (nmax > eig_chain_nmax())
+      throw ClrsdpError{CLRSDP_E_ARG, "eigenvalues: a block of n = " + std::to_string(nmax) +
+                                          " is too large for the on-chip vectors of eigblk_col (n <= " +
+                                          std::to_string(eig_chain_nmax()) + ")"};
+    size_t words = 0, parts = 0;
+    for (const MatDesc<T>& m : h) {
+      words += eigblk_ws_words(m.n);
+      parts += cdiv(m.n, EIG_R);
+    }
+    T* ws = own(std::vector<T>(words, T(0.0)));
+    double* am = own(std::vector<double>(parts, 0.0));
+    std::vector<EigBlkDesc<T>> e(h.size());
+    words = parts = 0;
+    for (size_t q = 0; q < h.size(); ++q) {
+      e[q] = EigBlkDesc<T>{h[q].A, ws + words, am + parts, h[q].n, h[q].lda};
+      words += eigblk_ws_words(h[q].n);
+      parts += cdiv(h[q].n, EIG_R);
+    }
+    ed = own(e);
+    eig_tri = eigblk_sturm_lds<T>(nmax, true) <= LDS_MAX;
+    // every instance that can ask for more than 64 KiB of dynamic LDS, outside any capture
+    static std::atomic<unsigned long long> ac{0}, at{0}, ag{0};
+    lds_attr_once(ac, (const void*)eigblk_col<T, EIG_R>, (int)LDS_MAX);
+    lds_attr_once(at, (const void*)eigblk_sturm<T, true>, (int)LDS_MAX);
+    lds_attr_once(ag, (const void*)eigblk_sturm<T, false>, (int)LDS_MAX);
+  }
+  void eigmin_chain(hipStream_t s, T* out) const {
+    constexpr int R = EIG_R;
+    const unsigned nm = (unsigned)h.size();
+    eigblk_amax<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed);
+    eigblk_sym<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed);
+    const size_t lds = eigblk_col_lds<T>(nmax);
+    for (int k = 0; k + 2 < nmax; ++k)
+      eigblk_col<T, R><<<dim3(cdiv(nmax - k - 1, R), nm), 64, lds, s>>>(ed, k);
+    if (eig_tri) eigblk_sturm<T, true><<<nm, 512, eigblk_sturm_lds<T>(nmax, true), s>>>(ed, out, R);
+    else eigblk_sturm<T, false><<<nm, 512, eigblk_sturm_lds<T>(nmax, false), s>>>(ed, out, R);
+    HIPCHK(hipGetLastError());
   }
   void potrf(hipStream_t s, int* info) const {
     if (h.empty()) return;
@@ -941,56 +1013,52 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   }
   void eigmin(hipStream_t s, T* out) const {
     if (h.empty()) return;
-    if constexpr (std::is_same<T, double>::value) {
-      if (nmax <= 128) {  // matrix in registers
-        // eigmin_split: one reflector chain wave + 8 bulk waves, the last 24 columns on the
-        // chain wave alone (no barriers)
-        eigmin_split<0, 24><<<(unsigned)h.size(), 576, 0, s>>>(d, out);
-        HIPCHK(hipGetLastError());
-        return;
-      }
-    }
-    // multi-word, n <= 64: an fp64 eigenpair refined at the word's width (eigmin_mx; the blocks
-    // it cannot certify go to eigmin_lds2 in a second, flagged launch) unless CLRSDP_EIG_MX=0
-    static const bool mx = !env_off("CLRSDP_EIG_MX");
-    if constexpr (!std::is_same<T, double>::value) {
-      if (mx && redo && nmax <= 64 && eigmx_lds_bytes<T>(nmax) + EIGMX_STATIC_LDS <= LDS_MAX &&
-          eig2_lds_bytes<T>(nmax) <= LDS_MAX && (sizeof(T) <= 16 || nmax <= 64)) {
-        static std::atomic<unsigned long long> attrm{0}, attr2r{0};
-        static const bool dbg = env_on("CLRSDP_EIGMX_STATS");
-        if (dbg) {  // (the diagnostics instance: per-block eta / lambda / Temple width)
-          static std::atomic<unsigned long long> attrd{0};
-          lds_attr_once(attrd, (const void*)eigmin_mx<T, 1>, (int)(LDS_MAX - EIGMX_STATIC_LDS));
-          eigmin_mx<T, 1><<<(unsigned)h.size(), 576, eigmx_lds_bytes<T>(nmax), s>>>(d, out, redo);
-        } else {
-          lds_attr_once(attrm, (const void*)eigmin_mx<T>, (int)(LDS_MAX - EIGMX_STATIC_LDS));
-          eigmin_mx<T><<<(unsigned)h.size(), 576, eigmx_lds_bytes<T>(nmax), s>>>(d, out, redo);
+    const unsigned nm = (unsigned)h.size();
+    switch (eig_dispatch(nmax, eig_blk)) {
+      case CLRSDP_EIG_K_SPLIT:
+        if constexpr (std::is_same<T, double>::value) {
+          // eigmin_split: one reflector chain wave + 8 bulk waves, the last 24 columns on the
+          // chain wave alone (no barriers)
+          eigmin_split<0, 24><<<nm, 576, 0, s>>>(d, out);
         }
-        HIPCHK(hipGetLastError());
-        // the flagged blocks (clustered lambda_min) at the full width; the others exit at once
-        lds_attr_once(attr2r, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
-        eigmin_lds2<T><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out, redo);
-        HIPCHK(hipGetLastError());
-        return;
+        break;
+      case CLRSDP_EIG_K_MX:
+        if constexpr (!std::is_same<T, double>::value) {
+          static std::atomic<unsigned long long> attrm{0}, attr2r{0};
+          static const bool dbg = env_on("CLRSDP_EIGMX_STATS");
+          if (dbg) {  // (the diagnostics instance: per-block eta / lambda / Temple width)
+            static std::atomic<unsigned long long> attrd{0};
+            lds_attr_once(attrd, (const void*)eigmin_mx<T, 1>, (int)(LDS_MAX - EIGMX_STATIC_LDS));
+            eigmin_mx<T, 1><<<nm, 576, eigmx_lds_bytes<T>(nmax), s>>>(d, out, redo);
+          } else {
+            lds_attr_once(attrm, (const void*)eigmin_mx<T>, (int)(LDS_MAX - EIGMX_STATIC_LDS));
+            eigmin_mx<T><<<nm, 576, eigmx_lds_bytes<T>(nmax), s>>>(d, out, redo);
+          }
+          HIPCHK(hipGetLastError());
+          // the flagged blocks (clustered lambda_min) at the full width; the others exit at once
+          lds_attr_once(attr2r, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
+          eigmin_lds2<T><<<nm, 512, eig2_lds_bytes<T>(nmax), s>>>(d, out, redo);
+        }
+        break;
+      case CLRSDP_EIG_K_LDS2:
+        if constexpr (!std::is_same<T, double>::value) {
+          static std::atomic<unsigned long long> attr2{0};
+          lds_attr_once(attr2, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
+          eigmin_lds2<T><<<nm, 512, eig2_lds_bytes<T>(nmax), s>>>(d, out);
+        }
+        break;
+      case CLRSDP_EIG_K_LDS: {
+        static std::atomic<unsigned long long> attr_t{0};
+        lds_attr_once(attr_t, (const void*)eigmin_lds<T, true>, (int)LDS_MAX);
+        eigmin_lds<T, true><<<nm, 512, eig_lds_bytes<T>(nmax), s>>>(d, out);
+        break;
       }
-    }
-    // multi-word: eigmin_lds2 (two barriers per column) where its column slots fit
-    if (!std::is_same<T, double>::value && eig2_lds_bytes<T>(nmax) <= LDS_MAX &&
-        (sizeof(T) <= 16 || nmax <= 64)) {  // (qd: 8 column slots per lane, n <= 64)
-      static std::atomic<unsigned long long> attr2{0};
-      lds_attr_once(attr2, (const void*)eigmin_lds2<T>, (int)LDS_MAX);
-      eigmin_lds2<T><<<(unsigned)h.size(), 512, eig2_lds_bytes<T>(nmax), s>>>(d, out);
-      HIPCHK(hipGetLastError());
-      return;
-    }
-    if (eig_lds_bytes<T>(nmax) <= LDS_MAX) {
-      const size_t lds = eig_lds_bytes<T>(nmax);
-      static std::atomic<unsigned long long> attr_t{0};
-      lds_attr_once(attr_t, (const void*)eigmin_lds<T, true>, (int)LDS_MAX);
-      eigmin_lds<T, true><<<(unsigned)h.size(), 512, lds, s>>>(d, out);
-    } else {
-      const size_t lds = sizeof(T) * (4 * (size_t)nmax + 256);
-      eigmin_batched<T><<<(unsigned)h.size(), 256, lds, s>>>(d, out);
+      case CLRSDP_EIG_K_BLK:
+        eigmin_chain(s, out);
+        return;
+      default:  // CLRSDP_EIG_K_BATCHED
+        eigmin_batched<T><<<nm, 256, sizeof(T) * (4 * (size_t)nmax + 256), s>>>(d, out);
+        break;
     }
     HIPCHK(hipGetLastError());
   }
@@ -4785,6 +4853,16 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
     g_last_error = e.what();
     return CLRSDP_E_HIP;
   }
+}
+
+int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel) {
+  if (!kernel || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
+  const bool chain = env_on("CLRSDP_EIG_BLK");
+  if (words == 1) *kernel = MatPlan<double>::eig_dispatch((int)nmax, chain);
+  else if (words == 2) *kernel = MatPlan<mw::dd>::eig_dispatch((int)nmax, chain);
+  else if (words == 4) *kernel = MatPlan<mw::qd>::eig_dispatch((int)nmax, chain);
+  else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  return CLRSDP_OK;
 }
 
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,

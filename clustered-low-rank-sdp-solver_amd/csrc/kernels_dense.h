@@ -9,6 +9,8 @@
 //                  for blocks past the on-chip kernels: diag, trsm and update steps per panel.
 //   eigmin_lds     lambda_min of a symmetric n <= 128 matrix held in LDS: Householder
 //                  tridiagonalisation + Sturm multisection (approx_eig_qr!, MPMP.jl:1857-1870).
+//   eigblk_*       the same for blocks past the LDS kernels, across workgroups: one launch per
+//                  column, then the multisection (CLRSDP_EIG_BLK=1, instead of eigmin_batched).
 #pragma once
 #include "kernels.h"
 
@@ -2230,6 +2232,250 @@ __global__ __launch_bounds__(512) void eigmin_lds2(const MatDesc<T>* __restrict_
   eigmin_lds2_dev<T, DBG>(descs[blockIdx.x], out, smem_raw);
 }
 #undef ANY_BELOW
+
+// ------------------------------------------------------------------------------------------
+// eigblk_*: lambda_min of blocks past the LDS kernels, tridiagonalised across workgroups
+// (CLRSDP_EIG_BLK=1, in place of the one-CU eigmin_batched).  A right-looking Householder
+// tridiagonalisation with one launch per column; nothing is handed over between workgroups
+// inside a launch, everything crosses at kernel boundaries, and no sum uses an atomic.
+//   eigblk_amax   per strip of R rows, the largest leading-limb magnitude (one partial each)
+//   eigblk_sym    ex = pow2_exp(max of the partials); A = (A + A^T) / 2^(ex + 1); clears the
+//                 state buffer that launch 0 reads
+//   eigblk_col    launch k.  State on entry, in the per-matrix scratch (two buffers, ping-pong):
+//                 v_{k-1}, p_{k-1} = beta A' v and beta_{k-1}; A is updated through reflector
+//                 k - 2.  Every workgroup (one wave) forms, redundantly and by the same
+//                 instruction sequence, w = p - (beta p^T v / 2) v, the true column k
+//                 A[:, k] - v w_k - w v_k, and from it dg[k], e2[k], v_k and beta_k
+//                 (eigmin_batched's tail > 0 rule: beta = 0, v = 0 for a column that is already
+//                 tridiagonal).  Then it owns R rows of the trailing matrix and all their columns
+//                 >= k + 1: one thread per row applies the pending rank-2 update, stores the entry
+//                 and accumulates A' v_k in ascending column order, so p_k[i] is one thread's sum
+//                 and lambda_min does not depend on R, on the grid or on the rest of the batch.
+//                 Column k itself is outside the region the launch writes.
+//   eigblk_sturm  one workgroup per matrix: the pending rank-2 update of the last 2 x 2, then the
+//                 multisection phase of eigmin_lds / eigmin_lds2 on (dg, e2).
+// A matrix with n <= k + 2 leaves launch k at once (batches mix sizes).
+// Scratch per matrix, in words of T: [v (n), p (n), beta] twice, dg (n), e2 (n).
+// ------------------------------------------------------------------------------------------
+template <class T>
+struct EigBlkDesc {
+  T* A;          // n x n, leading dimension lda (destroyed)
+  T* ws;         // eigblk_ws_words(n) words
+  double* amax;  // one partial per strip of the prepass
+  int n, lda;
+};
+constexpr size_t eigblk_ws_words(int n) { return 6 * (size_t)n + 2; }
+template <class T>
+__device__ __forceinline__ T* eigblk_state(const EigBlkDesc<T>& d, int q) {
+  return d.ws + (size_t)q * (2 * (size_t)d.n + 1);
+}
+// eigblk_col's dynamic LDS: v_k and w, indexed by row
+template <class T> constexpr size_t eigblk_col_lds(int n) { return 2 * sizeof(T) * (size_t)n; }
+// eigblk_sturm's: the multisection's scratch (2n + 14 doubles), one word, and the tridiagonal
+// when it is kept on chip
+constexpr size_t eigblk_sturm_scr(int n) { return ((2 * (size_t)n + 14) * 8 + 31) / 32 * 32; }
+template <class T> constexpr size_t eigblk_sturm_lds(int n, bool tri) {
+  return eigblk_sturm_scr(n) + sizeof(T) * (1 + (tri ? 2 * (size_t)n : 0));
+}
+
+template <class T, int R>
+__global__ __launch_bounds__(64) void eigblk_amax(const EigBlkDesc<T>* __restrict__ descs) {
+  const EigBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lane = threadIdx.x, i = blockIdx.x * R + lane;
+  if ((int)blockIdx.x * R >= n) return;
+  double amax = 0.0;
+  if (lane < R && i < n)
+    for (int j = 0; j < n; ++j) amax = fmax(amax, fabs(Num<T>::hi(d.A[i + (size_t)j * d.lda])));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+  if (lane == 0) d.amax[blockIdx.x] = amax;
+}
+
+// pow2_exp of the block from the strip partials (a max: the order does not matter)
+template <class T>
+__device__ __forceinline__ int eigblk_exp(const EigBlkDesc<T>& d, int R) {
+  double mx = 0.0;
+  for (int s = 0; s * R < d.n; ++s) mx = fmax(mx, d.amax[s]);
+  return pow2_exp(mx);
+}
+
+template <class T, int R>
+__global__ __launch_bounds__(64) void eigblk_sym(const EigBlkDesc<T>* __restrict__ descs) {
+  const EigBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lda = d.lda, lane = threadIdx.x, i = blockIdx.x * R + lane;
+  if ((int)blockIdx.x * R >= n) return;
+  const int ex = eigblk_exp(d, R);
+  if (lane >= R || i >= n) return;
+  // the thread of row i owns the pairs (i, j), (j, i) with j < i and the diagonal entry
+  T* A = d.A;
+  for (int j = 0; j < i; ++j) {
+    const T s = (scale2(A[i + (size_t)j * lda], -ex) + scale2(A[j + (size_t)i * lda], -ex)) * T(0.5);
+    A[i + (size_t)j * lda] = s;
+    A[j + (size_t)i * lda] = s;
+  }
+  A[i + (size_t)i * lda] = scale2(A[i + (size_t)i * lda], -ex);
+  // no reflector is pending when launch 0 (and the last launch of an n <= 2 block) reads buffer 0
+  T* st = eigblk_state(d, 0);
+  st[i] = T(0.0);
+  st[n + i] = T(0.0);
+  if (i == 0) st[2 * n] = T(0.0);
+}
+
+template <class T, int R>
+__global__ __launch_bounds__(64) void eigblk_col(const EigBlkDesc<T>* __restrict__ descs, int k) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const EigBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lda = d.lda, lane = threadIdx.x;
+  if (n <= k + 2) return;
+  const int i = k + 1 + (int)blockIdx.x * R + lane;  // the row of this thread
+  if (i - lane >= n) return;
+  T* vk = reinterpret_cast<T*>(smem_raw);  // n   reflector k, by row
+  T* w = vk + n;                           // n   w of reflector k - 1, by row
+  const T* __restrict__ vp = eigblk_state(d, k & 1);  // v_{k-1}, rows k .. n - 1
+  const T* __restrict__ pp = vp + n;                   // p_{k-1}
+  T* nx = eigblk_state(d, (k + 1) & 1);
+  T* A = d.A;
+  // ---- 1. w = p - (beta p^T v / 2) v, every workgroup alike
+  const T betap = vp[2 * n];
+  T pv = T(0.0);
+  for (int r = k + lane; r < n; r += 64) pv += pp[r] * vp[r];
+  pv = wave_sum_mw(pv);
+  const T Kc = betap * pv * T(0.5);
+  for (int r = k + lane; r < n; r += 64) w[r] = pp[r] - Kc * vp[r];
+  __syncthreads();
+  // ---- 2. the true column k, its diagonal entry and reflector
+  const T vpk = vp[k], wk = w[k];
+  T s = T(0.0);
+  for (int r = k + 1 + lane; r < n; r += 64) {
+    const T x = (A[r + (size_t)k * lda] - vp[r] * wk) - w[r] * vpk;
+    vk[r] = x;
+    s += x * x;
+  }
+  s = wave_sum_mw(s);
+  __syncthreads();
+  const T dk = (A[k + (size_t)k * lda] - vpk * wk) - wk * vpk;
+  const T x0 = vk[k + 1];
+  const T tail = s - x0 * x0;
+  const bool refl = tail > T(0.0);  // (the same in every lane) else already tridiagonal here
+  const T nrm = Num<T>::sqrt_(s);
+  const T alpha = sel(x0 > T(0.0), -nrm, nrm);
+  const T v0 = x0 - alpha;
+  const T e2k = sel(refl, alpha * alpha, x0 * x0);
+  const T beta = sel(refl, T(2.0) / (tail + v0 * v0), T(0.0));
+  __syncthreads();
+  if (refl) {
+    if (lane == 0) vk[k + 1] = v0;
+  } else {
+    for (int r = k + 1 + lane; r < n; r += 64) vk[r] = T(0.0);
+  }
+  __syncthreads();
+  // ---- 3. rows of this strip: pending rank-2 update, store, A' v_k in ascending columns
+  if (lane < R && i < n) {
+    constexpr int U = 128 / (int)sizeof(T);  // columns per batch, the next batch loaded ahead
+    const T vi = vp[i], wi = w[i];
+    T acc = T(0.0);
+    T* a = A + i + (size_t)(k + 1) * lda;
+    int j = k + 1;
+    const int nfull = (n - j) / U;
+    T ca[U], cv[U];
+    if (nfull > 0) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        ca[u] = a[(size_t)u * lda];
+        cv[u] = vp[j + u];
+      }
+    }
+    for (int b = 0; b < nfull; ++b) {
+      const bool more = b + 1 < nfull;
+      T na[U], nv[U];
+      if (more) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          na[u] = a[(size_t)(U + u) * lda];
+          nv[u] = vp[j + U + u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const T t = (ca[u] - vi * w[j + u]) - wi * cv[u];
+        a[(size_t)u * lda] = t;
+        acc += t * vk[j + u];
+      }
+      if (more) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          ca[u] = na[u];
+          cv[u] = nv[u];
+        }
+      }
+      a += (size_t)U * lda;
+      j += U;
+    }
+    for (; j < n; ++j, a += lda) {
+      const T t = (*a - vi * w[j]) - wi * vp[j];
+      *a = t;
+      acc += t * vk[j];
+    }
+    // ---- 4. this strip's rows of the next state
+    nx[i] = vk[i];
+    if (refl) nx[n + i] = beta * acc;
+    else nx[n + i] = T(0.0);
+  }
+  if (blockIdx.x == 0 && lane == 0) {
+    T* dg = d.ws + 2 * (2 * (size_t)n + 1);
+    dg[k] = dk;
+    dg[n + k] = e2k;
+    nx[2 * n] = beta;
+  }
+}
+
+// TRI: the tridiagonal is copied into LDS; otherwise the multisection reads it from the scratch
+// in global memory through the same pointers (2n words past the CU's LDS)
+template <class T, bool TRI>
+__global__ __launch_bounds__(512) void eigblk_sturm(const EigBlkDesc<T>* __restrict__ descs,
+                                                    T* __restrict__ out, int R) {
+  extern __shared__ __attribute__((aligned(32))) char smem_raw[];
+  const EigBlkDesc<T> d = descs[blockIdx.x];
+  const int n = d.n, lda = d.lda, tid = threadIdx.x;
+  T* scr = reinterpret_cast<T*>(smem_raw);
+  T* Wv = reinterpret_cast<T*>(smem_raw + eigblk_sturm_scr(n));
+  T* dgg = d.ws + 2 * (2 * (size_t)n + 1);
+  T* e2g = dgg + n;
+  const int ex = eigblk_exp(d, R);
+  if (tid == 0) {
+    const T* A = d.A;
+    if (n == 1) {
+      dgg[0] = A[0];
+    } else {
+      // reflector n - 3 (none for n = 2: eigblk_sym cleared buffer 0) is pending on the last 2 x 2
+      const T* vp = eigblk_state(d, (n - 2) & 1);
+      const T* pp = vp + n;
+      const int r0 = n - 2, r1 = n - 1;
+      const T v0 = vp[r0], v1 = vp[r1];
+      const T Kc = vp[2 * n] * (pp[r0] * v0 + pp[r1] * v1) * T(0.5);
+      const T w0 = pp[r0] - Kc * v0, w1 = pp[r1] - Kc * v1;
+      dgg[r0] = (A[r0 + (size_t)r0 * lda] - v0 * w0) - w0 * v0;
+      dgg[r1] = (A[r1 + (size_t)r1 * lda] - v1 * w1) - w1 * v1;
+      const T e = (A[r1 + (size_t)r0 * lda] - v1 * w0) - w1 * v0;
+      e2g[r0] = e * e;
+    }
+  }
+  __syncthreads();
+  const T* dg = dgg;
+  const T* e2 = e2g;
+  if constexpr (TRI) {
+    T* dl = Wv + 1;
+    T* el = dl + n;
+    for (int q = tid; q < n; q += 512) {
+      dl[q] = dgg[q];
+      if (q + 1 < n) el[q] = e2g[q];
+    }
+    __syncthreads();
+    dg = dl;
+    e2 = el;
+  }
+  eig_multisection<T, true>(dg, e2, n, scr, Wv, out, ex);
+}
 
 // ------------------------------------------------------------------------------------------
 // eigmin_mx (round 4): multi-word lambda_min (n <= 64) from an fp64 eigenpair refined at the

@@ -356,6 +356,15 @@ def eigmin(blocks, precision_words: int = 1, device: int = 0):
     return from_planes(out, len(mats), w)
 
 
+def eigmin_kernel(nmax: int, precision_words: int = 1) -> int:
+    """Which kernel ``eigmin`` (and the STEP stage's eigen launches) takes for a batch whose largest
+    block is ``nmax``, under the current environment: one of ``_lib.EIG_K_*``
+    (clrsdp_eigmin_kernel; a host-only query, no device and no launch)."""
+    k = C.c_int32(-1)
+    _lib.check(_lib.lib().clrsdp_eigmin_kernel(int(precision_words), int(nmax), C.byref(k)))
+    return k.value
+
+
 def getrf(blocks, precision_words: int = 1, device: int = 0, raw_limbs: bool = False):
     """Partially pivoted LU of each square block, ``A[perm] = L U``, at fp64 / double-double /
     quad-double (clrsdp_getrf: approx_lu!, MPMP.jl:1436, 1501, as the solver's LU path runs it).

@@ -358,9 +358,42 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
  * magnitude on load and lambda_min multiplied back (exact), so the result is relative to the
  * block's norm at any scale; supported (and tested) for blocks whose largest |entry| lies in
  * [2^-600, 2^600].  Outside it the trailing limbs of a multi-word entry or of the result can
- * fall into the subnormal range and the accuracy degrades towards fp64's. */
+ * fall into the subnormal range and the accuracy degrades towards fp64's.
+ *
+ * The kernel is chosen by the word width and the largest block of the call (nmax);
+ * clrsdp_eigmin_kernel reports it:
+ *   words | kernel by nmax
+ *   1     | eigmin_split <= 128; eigmin_lds 129-138; eigmin_batched >= 139
+ *   2     | eigmin_mx (+ eigmin_lds2 for the blocks it cannot certify) <= 64; eigmin_lds2 65-93;
+ *         | eigmin_lds 94-96; eigmin_batched >= 97
+ *   4     | eigmin_mx (+ eigmin_lds2) <= 64; eigmin_lds 65-66; eigmin_batched >= 67
+ * (CLRSDP_EIG_MX=0: eigmin_lds2 in eigmin_mx's range.)
+ * Size bound of the default: eigmin_batched is one workgroup per block and asks for
+ * sizeof(word) (4 nmax + 256) bytes of dynamic LDS and never sets the kernel's
+ * max-dynamic-LDS attribute.  By reading, not by running: the request passes 64 KiB (HIP's
+ * documented limit without the attribute) beyond nmax = 1984 (fp64), 960 (double-double) and 448
+ * (quad-double), and the 160 KiB of a CU -- which is what hipFuncGetAttributes reports as the
+ * kernel's limit on an MI355X -- beyond 5056, 2496 and 1216.  The default has not been run past
+ * the first figures; past the second the runtime refuses the launch (CLRSDP_E_HIP).
+ * CLRSDP_EIG_BLK=1 (environment, read when the call builds its plan; default off) sends every
+ * batch of eigmin_batched's range to the eigblk_* chain instead: the tridiagonalisation runs
+ * across workgroups with one launch per column, the multisection of eigmin_lds follows, and
+ * lambda_min of a block is bitwise independent of the rest of the batch.  Its bound is the two
+ * on-chip vectors of a column step, 2 nmax words in 160 KiB: beyond this entry point's 4096 at
+ * fp64 and double-double, nmax <= 2560 at quad-double (larger: CLRSDP_E_ARG). */
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                       const double* A, double* min_eig);
+
+/* Which kernel clrsdp_eigmin (and the STEP stage's eigen launches) takes for a batch at `words`
+ * whose largest block is nmax (1 .. 4096), under the current environment.  A host-only query:
+ * no device is touched and nothing is launched. */
+#define CLRSDP_EIG_K_SPLIT 0    /* eigmin_split (fp64, matrix in registers)                  */
+#define CLRSDP_EIG_K_MX 1       /* eigmin_mx, then eigmin_lds2 on the flagged blocks         */
+#define CLRSDP_EIG_K_LDS2 2     /* eigmin_lds2                                               */
+#define CLRSDP_EIG_K_LDS 3      /* eigmin_lds                                                */
+#define CLRSDP_EIG_K_BATCHED 4  /* eigmin_batched (one workgroup per block, global memory)   */
+#define CLRSDP_EIG_K_BLK 5      /* eigblk_* chain across workgroups (CLRSDP_EIG_BLK=1)       */
+int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel);
 
 /* Partially pivoted LU of each block in place, A_b[perm_b] = L_b U_b (approx_lu!, MPMP.jl:1436,
  * 1501; the factor of approx_inv!, 781), as the solver's LU path runs it.  A: nblocks blocks of
