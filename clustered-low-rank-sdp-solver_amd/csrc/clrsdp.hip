@@ -2685,11 +2685,50 @@ struct Solver final : HandleBase {
     // + the OR (update guard), then the SCHUR clock stamps (8-byte aligned)
     stat_stamp_off = (stat_info_off + (info_count + 1) * sizeof(int) + 7) / 8 * 8;
     stat_bytes = stat_stamp_off + 6 * sizeof(unsigned long long);
-    stat_dev = dmalloc<char>(stat_bytes);
-    HIPCHK(hipHostMalloc((void**)&stat_host, stat_bytes, hipHostMallocDefault));
+    // (both blocks carry one more 8-byte word behind the copied bytes: the device's count of
+    // published bodies and the host's sequence word, see publish_ok())
+    stat_dev = dmalloc<char>(stat_bytes + 8);
+    HIPCHK(hipMemset(stat_dev + stat_bytes, 0, 8));
+    HIPCHK(hipHostMalloc((void**)&stat_host, stat_bytes + 8,
+                         hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(stat_host, 0, stat_bytes + 8);
+    HIPCHK(hipHostGetDevicePointer((void**)&stat_host_dev, stat_host, 0));
     sc = reinterpret_cast<T*>(stat_dev);
     info = reinterpret_cast<int*>(stat_dev + stat_info_off);
     stamps = reinterpret_cast<unsigned long long*>(stat_dev + stat_stamp_off);
+  }
+  // ---- the synchronous fp64 loop body at one rank publishes its stat block itself: its last
+  // scalar launch (which == 3) stores the block into the host mirror and then a sequence word,
+  // and iterate_once() polls that word -- no copy node and no stream sync between two bodies.
+  // Every other path (the pipelined loop, run_stage, initial(), multi-word, sharded, per-stage
+  // timing, the LU-fallback plans, a handle without graph replay) keeps stat_fetch().  A body
+  // whose capture failed and that was enqueued eagerly instead publishes like the replayed one.
+  char* stat_host_dev = nullptr;  // the mirror's device address
+  bool seam_pub = !env_off("CLRSDP_SEAM_PUB");
+  bool pub_body = false;          // the body being enqueued publishes (read by scalars(.., 3))
+  bool publish_ok(int pd_feas) const {
+    return seam_pub && std::is_same<T, double>::value && world == 1 && pd_feas >= 0 &&
+           graph_ok() && !lu_sq() && !lu_x();
+  }
+  unsigned long long pub_seq_now() const {
+    return __atomic_load_n(reinterpret_cast<const unsigned long long*>(stat_host + stat_bytes),
+                           __ATOMIC_ACQUIRE);
+  }
+  // wait until the sequence word leaves `last`; the stream is queried between polls, so a stream
+  // that has completed or failed without publishing is an error and not a spin
+  void pub_wait(unsigned long long last) {
+    for (unsigned spin = 1;; ++spin) {
+      if (pub_seq_now() != last) return;
+      if ((spin & 1023u) == 0) {
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipSuccess) {
+          if (pub_seq_now() != last) return;
+          throw ClrsdpError{CLRSDP_E_HIP, "the loop body completed without publishing its stat block"};
+        }
+        if (q != hipErrorNotReady) HIPCHK(q);
+        (void)hipGetLastError();  // ("not ready" is no error for the launches checked later)
+      }
+    }
   }
   // copy scalars + status to the host mirror and wait
   void stat_fetch() {
@@ -2705,6 +2744,13 @@ struct Solver final : HandleBase {
     p.stamps = zero_info ? stamps : nullptr;
     p.guard = info;
     p.nguard = info_count;
+    if (which == 3 && pub_body) {
+      p.pub_n8 = (int)(stat_bytes / 8);
+      p.pub_src = reinterpret_cast<const unsigned long long*>(stat_dev);
+      p.pub_dst = reinterpret_cast<unsigned long long*>(stat_host_dev);
+      p.pub_cnt = reinterpret_cast<unsigned long long*>(stat_dev + stat_bytes);
+      p.pub_seq = reinterpret_cast<unsigned long long*>(stat_host_dev + stat_bytes);
+    }
     zero_info = false;
     launch_folds<T>(stream, sc, p, pend, which);  // at most 6 folded reductions per launch
     pend.clear();
@@ -3147,6 +3193,30 @@ struct Solver final : HandleBase {
       sym(dY, dY, 0);
     });
   }
+  // t_j = L_j^-1 rhs_j and the slabs W_j^T t_j: the part of the batched solve that needs no Q^-1
+  // (it waits for X21 / L_j^-1 where a side stream produced them).  head_ahead: the loop body has
+  // run it on the side stream already, beside chol(Q)
+  bool head_ahead = false;
+  bool qchol_main = !env_off("CLRSDP_QCHOL_MAIN");
+  void solve_head() {
+    if (pending_x21) {
+      HIPCHK(hipStreamWaitEvent(stream, ev_x21, 0));
+      pending_x21 = false;
+    }
+    if (pending_sinv) {
+      HIPCHK(hipStreamWaitEvent(stream, ev_sinv, 0));
+      pending_sinv = false;
+    }
+    if (reg_S) {
+      q_t.launch(stream, 1.0, 0.0);
+    } else if (s_split) {
+      q_t2.launch(stream, 1.0, 0.0);
+    } else {
+      vlin(tvec, rhs, 1.0, nullptr, 0, nullptr, 0, nx);
+      t_t.launch(stream, false);
+    }
+    p_Wt.launch(stream, 1.0, 0.0);
+  }
   // the three-stage solve and dx as separate batched launches (any word type / rank count)
   void direction_solves(int tag) {
     // t_j = L_j^-1 rhs_j ;  u = sum_j W_j^T t_j ;  dy = Q^-1 (p - u) ; dx_j = L_j^-T (t_j + W_j dy)
@@ -3180,19 +3250,8 @@ struct Solver final : HandleBase {
         return;
       }
     }
-    if (pending_sinv) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_sinv, 0));
-      pending_sinv = false;
-    }
-    if (reg_S) {
-      q_t.launch(stream, 1.0, 0.0);
-    } else if (s_split) {
-      q_t2.launch(stream, 1.0, 0.0);
-    } else {
-      vlin(tvec, rhs, 1.0, nullptr, 0, nullptr, 0, nx);
-      t_t.launch(stream, false);
-    }
-    p_Wt.launch(stream, 1.0, 0.0);
+    if (head_ahead) head_ahead = false;  // (the loop body ran it on the side stream, beside chol(Q))
+    else solve_head();
     // fp64 with the explicit Q^-1: r = p - sum of the slabs and dy = Q^-1 r in one launch
     // (slab_qsolve)
     bool fused_done = false;
@@ -3523,7 +3582,8 @@ struct Solver final : HandleBase {
     //   after MU_R:  P = sum x_i A_i - X - C                      (state only)
     //   after SCHUR: d, the p-slabs, the maxima (A_Y from SCHUR); Z = X^-1 (P Y - R), U = Z V
     //                and rhs = -d - Tr(A_* Z)                     (the predictor's trace_A)
-    //   after FACTOR's Q sum: chol(Q) -> L_Q^-1, Q^-1
+    //   after FACTOR's Q sum: chol(Q) -> L_Q^-1, Q^-1 -- or, with q_main below, p, the guarded
+    //                copy and the head of the predictor's solve while the main stream factors Q
     const hipStream_t main_s = stream;
     auto side = [&](hipEvent_t ev, auto&& work) {
       HIPCHK(hipEventRecord(ev, main_s));
@@ -3569,27 +3629,50 @@ struct Solver final : HandleBase {
     });
     mark(CLRSDP_STAGE_FACTOR);
     factor_local(true);
+    // fp64 at one rank with the batched Cholesky solves: chol(Q) -> L_Q^-1, Q^-1 stays on the main
+    // stream right behind the Q sum (they are the critical path), and what the main stream used
+    // to run meanwhile goes to the side stream behind the right-hand side: p and the error folds,
+    // the guarded copy of p, and the head of the predictor's solve (t = L^-1 rhs, the slabs
+    // W^T t), none of which reads Q.  One join, just before the Q solve; no fork for chol(Q).
+    const bool q_main = qchol_main && std::is_same<T, double>::value && world == 1 && timing != 1 &&
+                        nc() && !lu_sq() && !cls_on;
     {
       if (w_split) HIPCHK(hipStreamWaitEvent(aux, ev_w, 0));
       StreamSwitch on_aux(stream, aux);
       direction_rhs();
-      HIPCHK(hipEventRecord(ev_r, aux));
+      if (!q_main) HIPCHK(hipEventRecord(ev_r, aux));
     }
-    // side stream: chol(Q) -> L_Q^-1, waited for just before the first Q solve
     HIPCHK(hipEventRecord(ev_qa, main_s));
     HIPCHK(hipStreamWaitEvent(aux, ev_qa, 0));
-    {
-      StreamSwitch on_aux(stream, aux);
+    if (q_main) {
       factor_q();
+      if (capturing && inject_capture_fail)
+        throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
+      {
+        // (behind ev_qa: W, L^-1 and the halt word come from the main stream)
+        StreamSwitch on_aux(stream, aux);
+        residuals_finish(true);
+        if (keep_res) copy_guarded(pres, pvec, n_y);
+        solve_head();
+        head_ahead = true;
+        HIPCHK(hipEventRecord(ev_r, aux));
+      }
+      HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
+    } else {
+      // side stream: chol(Q) -> L_Q^-1, waited for just before the first Q solve
+      {
+        StreamSwitch on_aux(stream, aux);
+        factor_q();
+      }
+      HIPCHK(hipEventRecord(ev_q, aux));
+      pending_q = true;
+      if (capturing && inject_capture_fail)
+        throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
+      mark(CLRSDP_STAGE_RESIDUALS);
+      HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
+      residuals_finish(timing != 1);
+      if (keep_res) copy_guarded(pres, pvec, n_y);
     }
-    HIPCHK(hipEventRecord(ev_q, aux));
-    pending_q = true;
-    if (capturing && inject_capture_fail)
-      throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
-    mark(CLRSDP_STAGE_RESIDUALS);
-    HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
-    residuals_finish(timing != 1);
-    if (keep_res) copy_guarded(pres, pvec, n_y);
     HIPCHK(hipGetLastError());
     mark(CLRSDP_STAGE_PREDICTOR);
     direction_rest(4);   // Z, U and rhs came from the side stream
@@ -3629,6 +3712,7 @@ struct Solver final : HandleBase {
   // launch never waits for the previous launch of the same executable graph)
   hipGraphExec_t gexec[4] = {nullptr, nullptr, nullptr, nullptr};
   clrsdp_params gprm[4];
+  bool gpub[4] = {false, false, false, false};  // captured as a publishing body (publish_ok())
   unsigned graph_launches = 0;
   // multi-word bodies are enqueued eagerly by default: C5 (qd) 719-730 against 672-706 it/s,
   // C4 (dd) 620-625 against 600-617 with the replayed graph (A/B, round 4); fp64 keeps the
@@ -3665,7 +3749,7 @@ struct Solver final : HandleBase {
   void launch_graph(const clrsdp_params* prm, int pd_feas) {
     // (one executable for every pipelined body measured the same as two alternating, round 4)
     const int g = pd_feas < 0 ? 2 + (graph_launches++ & 1) : (pd_feas ? 1 : 0);
-    if (!gexec[g] || std::memcmp(&gprm[g], prm, sizeof(*prm)) != 0) {
+    if (!gexec[g] || std::memcmp(&gprm[g], prm, sizeof(*prm)) != 0 || gpub[g] != pub_body) {
       if (gexec[g]) HIPCHK(hipGraphExecDestroy(gexec[g]));
       gexec[g] = nullptr;
       hipGraph_t graph = nullptr;
@@ -3691,6 +3775,7 @@ struct Solver final : HandleBase {
       HIPCHK(hipGraphInstantiate(&gexec[g], graph, nullptr, nullptr, 0));
       HIPCHK(hipGraphDestroy(graph));
       gprm[g] = *prm;
+      gpub[g] = pub_body;
     }
     HIPCHK(hipGraphLaunch(gexec[g], stream));
   }
@@ -3709,6 +3794,7 @@ struct Solver final : HandleBase {
     pending_q = pending_x21 = pending_sinv = false;
     ty_ahead = false;
     w_split = false;
+    head_ahead = false;
     dy_dot_ready = false;
     alpha_fused = false;
     fuse_alpha = false;
@@ -3740,11 +3826,25 @@ struct Solver final : HandleBase {
     }
   }
   int iterate_once(const clrsdp_params* prm, int pd_feas, clrsdp_iter_stats* st) {
-    if (graph_ok()) launch_graph_or_eager(prm, pd_feas);
-    else enqueue_iteration(prm, pd_feas);
+    // (a publishing body: its last scalar launch fills the host mirror, see publish_ok())
+    const bool pub = publish_ok(pd_feas);
+    const unsigned long long seq0 = pub ? pub_seq_now() : 0ull;
+    if (graph_ok()) {
+      pub_body = pub;
+      try {
+        launch_graph_or_eager(prm, pd_feas);
+      } catch (...) {
+        pub_body = false;
+        throw;
+      }
+      pub_body = false;
+    } else {
+      enqueue_iteration(prm, pd_feas);
+    }
     res_from_copy = false;
     std::memset(st, 0, sizeof(*st));
-    stat_fetch();
+    if (pub) pub_wait(seq0);
+    else stat_fetch();
     read_stats(st);
     if (timing == 2) {  // the SCHUR stage of the body that just ran (device clock stamps)
       const unsigned long long* t = reinterpret_cast<const unsigned long long*>(stat_host + stat_stamp_off);
@@ -3770,6 +3870,9 @@ struct Solver final : HandleBase {
     }
     const int rc = check_info();
     st->status = rc;
+    // (a failed body may be followed by fallback(), which destroys the graphs: the replay has
+    // published, but the runtime may not have retired it yet)
+    if (pub && rc != CLRSDP_OK) HIPCHK(hipStreamSynchronize(stream));
     return rc;
   }
   // 0: off (graph replay); 1: every stage between HIP events, no graph; 2: graph replay, and the

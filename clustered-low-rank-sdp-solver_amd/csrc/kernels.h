@@ -3487,6 +3487,15 @@ template <class T> struct ScalarParams {
   // fallback re-runs it with the control of the body before)
   const int* guard;
   int nguard;
+  // which == 3 at the end of a captured fp64 loop body: the launch publishes the stat block
+  // pub_src[0..pub_n8) (8-byte words: the slots, the status words, the SCHUR stamps) into the
+  // pinned host mirror pub_dst, then stores the body count ++*pub_cnt into pub_seq (host memory)
+  // with release ordering at system scope; the host polls that word instead of a copy + sync
+  int pub_n8;
+  const unsigned long long* pub_src;
+  unsigned long long* pub_dst;
+  unsigned long long* pub_cnt;
+  unsigned long long* pub_seq;
   FoldRed<T> red[6];
 };
 
@@ -3716,6 +3725,20 @@ __global__ __launch_bounds__(64) void scalar_kernel(T* scg, ScalarParams<T> p, i
     for (int e = lane; e < p.nguard; e += 64) fl = fl || p.guard[e] != 0;
   const bool failed = __any(fl);
   if (lane == 0) scalar_logic(sc, p, which, failed);
+  if (which == 3 && p.pub_dst) {
+    // lane 0's slot stores above are read back by the other lanes: behind a barrier, past the L1
+    // (agent-scope loads); the status words and stamps come from earlier launches
+    __syncthreads();
+    for (int e = lane; e < p.pub_n8; e += 64)
+      p.pub_dst[e] = __hip_atomic_load(p.pub_src + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // one wave: the release below orders every lane's stores above before the sequence word
+    __syncthreads();
+    if (lane == 0) {
+      const unsigned long long n = *p.pub_cnt + 1ull;
+      *p.pub_cnt = n;
+      __hip_atomic_store(p.pub_seq, n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 }
 
 }  // namespace clrsdp
