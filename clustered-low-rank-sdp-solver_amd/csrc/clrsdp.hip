@@ -225,6 +225,33 @@ struct StreamSwitch {
   StreamSwitch& operator=(const StreamSwitch&) = delete;
 };
 
+// work that one stream produces for another: an event and "somebody still has to wait for it".
+// The Solver lists its hand-offs once (Solver::handoffs); creation, destruction, the drain at the
+// end of a loop body and reset_body_state() walk that list
+struct Handoff {
+  hipEvent_t ev = nullptr;
+  bool on = false;
+  void create() { HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
+  void destroy() {
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+  }
+  void signal(hipStream_t producer) {
+    HIPCHK(hipEventRecord(ev, producer));
+    on = true;
+  }
+  // wait: the consumer waits if armed, and a later consumer on another stream still will
+  void wait(hipStream_t consumer) const {
+    if (on) HIPCHK(hipStreamWaitEvent(consumer, ev, 0));
+  }
+  void join(hipStream_t consumer) {  // the last (usually the only) consumer
+    wait(consumer);
+    on = false;
+  }
+  void disarm() { on = false; }
+  bool armed() const { return on; }
+};
+
 // the plans own their device descriptor arrays (freed with the plan; plans are never copied)
 struct PlanBase {
   std::vector<void*> owned_dev;
@@ -1397,9 +1424,6 @@ struct Solver final : HandleBase {
   ChainPlan c_stepX, c_stepY;             // the step-length congruences apart (xy_ov)
   MatPlan<T> e_Xs, e_Ys;                  // their eigen launches apart
   bool xy_ov_ok = false;   // the overlapped step length is configured (small batches, opt-in)
-  bool xy_ov_body = false; // enqueue_iteration: the corrector may fork the X step length
-  bool xy_ov = false;      // it did: STEP runs the Y half and joins ev_stx
-  hipEvent_t ev_dxo = nullptr, ev_stx = nullptr;
   // fp64 FACTOR with every dim_S <= 256 (fac2): f_a = {W = L^-1 B | L21^T = L11^-1 S12, W1} and
   // f_b = {W^T W | S22 - L21 L21^T, W1^T W1, B2 - L21 W1} as mixed batches, then (dim_S > 128)
   // chol_inv(S22), f_c: W2 = L22^-1 B2', f_d: slab += W2^T W2 (measured 1% faster than one
@@ -1415,17 +1439,14 @@ struct Solver final : HandleBase {
   // m = L = 1 with rank-1 samples): no scale_cols launch, no scaled copy of V
   bool wa_fused = false;
   GemmPlan<T> p_wA_Ps, p_wA_dXs;
-  bool pending_x21 = false;  // the solves wait for X21 (side stream, iterate)
-  hipEvent_t ev_x2 = nullptr, ev_x21 = nullptr;
   // multi-word S_j / Q beyond reg_nmax in the split form: potrf on the critical path,
   // L^-1 by four-wave triangular solves of the identity (S_j: on aux2, off the critical path),
   // then the same GEMV solves as the explicit-inverse path
-  bool s_split = false, q_split = false, pending_sinv = false;
+  bool s_split = false, q_split = false;
   bool qf_fresh = false;  // sum_q_slabs wrote Qf = Q for this iteration's factor_q_
   T *SLi = nullptr, *QLi = nullptr;  // L^-1 of the S_j and of Q
   TrsmPlan<T> t_Sinv, t_Qinv;
   GemmPlan<T> q_t2, q_dx2, q_qinv2;
-  hipEvent_t ev_sp = nullptr, ev_sinv = nullptr;
   MatPlan<T> e_XY;                        // both step-length eigenproblems in one launch
   // LU fallback plans (built on the first switch)
   LuPlan<T> lu_S, lu_Q, lu_X;
@@ -1439,8 +1460,6 @@ struct Solver final : HandleBase {
   // paired Hadamard tiles; clusters with L > 1 or ranks != 1 are summed from G (BX arena)
   bool fast_schur = false;
   GemmPlan<T> p_txy, p_ty;  // V^T X^-1 (SCHUR) and V^T Y (ahead on the side stream in a loop body)
-  bool ty_ahead = false;     // p_ty already enqueued on the side stream (joined by ev_ty)
-  hipEvent_t ev_ty = nullptr;
   PairTileDesc* d_ptd = nullptr;
   TileRef* d_pt2d = nullptr;
   int n_ptiles = 0;
@@ -1464,7 +1483,7 @@ struct Solver final : HandleBase {
   // <X + dX, Y + dY> partials from the predictor's dY chain (dotp, dy_dot_cnt of them)
   T* dotp = nullptr;
   int dy_dot_cnt = 0;
-  bool dy_dot_ok = false, dy_dot_ready = false;
+  bool dy_dot_ok = false;
   // fp64 cluster solves in two launches (cl_solve_t / cl_solve_dx): one descriptor per cluster,
   // cls_nrb 64-row blocks per cluster (the partial slabs: nc x cls_nrb x n_y in pslab)
   std::vector<ClSolveDesc> h_cls;
@@ -1501,9 +1520,45 @@ struct Solver final : HandleBase {
   // side stream: the local residuals overlap the Schur factorisation, chol(Q) overlaps the
   // first part of the predictor (iterate only; run_stage stays serial)
   hipStream_t aux = nullptr, aux2 = nullptr;
-  hipEvent_t ev_m = nullptr, ev_x = nullptr, ev_s = nullptr, ev_r = nullptr, ev_qa = nullptr,
-             ev_q = nullptr, ev_join = nullptr, ev_fa = nullptr, ev_w = nullptr, ev_join2 = nullptr;
-  bool pending_q = false;
+  // events that only order a fork (fork() below) or a join written out where it happens (EV_R in
+  // enqueue_iteration, EV_JOIN / EV_JOIN2 after a failed capture): nobody keeps a flag for them
+  enum ForkEv { EV_M, EV_S, EV_QA, EV_R, EV_FA, EV_X2, EV_SP, EV_DXO, EV_JOIN, EV_JOIN2, N_FORK_EV };
+  hipEvent_t fev[N_FORK_EV] = {};
+  // work on `to` behind everything enqueued on `stream` so far: `stream` is `to` while work() runs
+  template <class F>
+  void fork(hipEvent_t e, hipStream_t to, F&& work) {
+    HIPCHK(hipEventRecord(e, stream));
+    HIPCHK(hipStreamWaitEvent(to, e, 0));
+    StreamSwitch on_to(stream, to);  // restored on scope exit, also when a launch throws
+    work();
+  }
+  // The hand-offs of a loop body: each is signalled on the stream that produced the work and
+  // joined where it is first read.  A new one is a new member and one line in handoffs[]; the
+  // order of handoffs[] is the order of the drain at the end of enqueue_iteration.
+  Handoff h_stx;   // aux -> main: lambda_min of the X step (direction_rest, xy_ov); joined by st_step
+  Handoff h_q;     // aux -> main: L_Q^-1, Q^-1 (enqueue_iteration, !q_main); joined before the Q solve
+  Handoff h_x21;   // aux2 -> the stream of solve_head / direction_solves: X21 (factor_local, fac2 with S22)
+  Handoff h_sinv;  // aux2 -> the stream of solve_head: L_j^-1 (factor_local, s_split)
+  Handoff h_ty;    // aux -> main: V^T Y (enqueue_iteration, ty_side); joined by st_schur
+  Handoff h_w;     // aux2 -> main (factor_local, wait) and aux (enqueue_iteration, join): W1^T W1, B2'
+  Handoff* const handoffs[6] = {&h_stx, &h_q, &h_x21, &h_sinv, &h_ty, &h_w};
+  // What changes how ONE loop body is enqueued; all false between bodies (reset_body_state()).
+  //   fuse_r       set by enqueue_iteration before MU_R (fp64, not timing mode 1), cleared by it
+  //                after XINV: R = mu_p I - XY rides in XINV's launch (st_mu_r, st_xinv)
+  //   fuse_alpha   set by enqueue_iteration before CORRECTOR_R (not timing mode 1), cleared by it
+  //                after UPDATE: st_step leaves alpha to UPDATE's launch
+  //   alpha_fused  set by st_step when it did so, cleared by the st_update that forms alpha
+  //   xy_ov_body   set and cleared by enqueue_iteration beside fuse_alpha: the corrector's
+  //                direction_rest may fork the X step length (it then signals h_stx)
+  //   head_ahead   set by enqueue_iteration (q_main) after solve_head ran on the side stream,
+  //                cleared by the predictor's direction_solves, which then skips it
+  //   dy_dot_ready set by the predictor's direction_rest when its dY chain left the
+  //                <X + dX, Y + dY> partials, cleared by st_corrector_r (and by a new state:
+  //                set_state, restore_state)
+  struct BodyFlags {
+    bool fuse_r = false, fuse_alpha = false, alpha_fused = false, xy_ov_body = false,
+         head_ahead = false, dy_dot_ready = false;
+  } body;
   float phase_ms[CLRSDP_NUM_STAGES];
 
   int nb() const { return (int)lb.size(); }
@@ -1604,9 +1659,8 @@ struct Solver final : HandleBase {
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&aux2, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&ev_m, &ev_x, &ev_s, &ev_r, &ev_qa, &ev_q, &ev_x2, &ev_x21, &ev_ty, &ev_join,
-                          &ev_fa, &ev_w, &ev_join2, &ev_sp, &ev_sinv, &ev_dxo, &ev_stx})
-      HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t& e : fev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Handoff* h : handoffs) h->create();
     allocate();
     build_plans();
   }
@@ -1635,8 +1689,10 @@ struct Solver final : HandleBase {
       if (r) (void)hipHostFree(r);
     for (auto& e : ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : seg_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ev_m, ev_x, ev_s, ev_r, ev_qa, ev_q, ev_x2, ev_x21, ev_ty, ev_join, ev_fa, ev_w,
-                         ev_join2, ev_sp, ev_sinv, ring_ev[0], ring_ev[1]})
+    for (hipEvent_t e : fev)
+      if (e) (void)hipEventDestroy(e);
+    for (Handoff* h : handoffs) h->destroy();
+    for (hipEvent_t e : ring_ev)
       if (e) (void)hipEventDestroy(e);
     for (hipGraphExec_t g : gexec)
       if (g) (void)hipGraphExecDestroy(g);
@@ -2548,7 +2604,7 @@ struct Solver final : HandleBase {
   }
 
   void set_state(const double* xh, const double* Xh, const double* yh, const double* Yh) override {
-    dy_dot_ready = false;  // (a new state: CORRECTOR_R sums <X + dX, Y + dY> itself)
+    body.dy_dot_ready = false;  // (a new state: CORRECTOR_R sums <X + dX, Y + dY> itself)
     for (int c = 0; c < nc(); ++c) put(x + c_xoff[c], xh, tot_x, xoff_g[oc[c]], Ds[oc[c]]);
     for (const LBlk& b : lb) {
       put(X + b.off, Xh, tot_blk, blkoff_g[b.gjl], (int64_t)b.n * b.n);
@@ -2799,13 +2855,12 @@ struct Solver final : HandleBase {
   // ---------------- stages
   void st_mu_r(const clrsdp_params* prm, int pd_feas) {
     mu_scalars(prm, pd_feas);
-    if (!fuse_r) mu_r_gemm();
+    if (!body.fuse_r) mu_r_gemm();
   }
   // (round 6) a loop body at fp64 forms R = mu_p I - XY in XINV's launch, beside
   // X^-1 = L^-T L^-1: a mixed batch (gemm_f64_dyn, the mu_p diagonal from the scalar slot) instead
   // of a 128^3 GEMM launch of its own on the critical path before chol_inv(X, Y) -- R is first
   // read by the predictor's Z after SCHUR.  (The per-stage timing mode keeps the separate launch.)
-  bool fuse_r = false;
   GemmPlan<T> p_xir;
   // mu = <X,Y>/dim, mu_p (and the status words cleared, the halt word decided)
   void mu_scalars(const clrsdp_params* prm, int pd_feas) {
@@ -2842,15 +2897,15 @@ struct Solver final : HandleBase {
       ci_XY.launch(stream, info);
       if (lu_x()) {
         xinv_lu();
-        if (fuse_r) mu_r_gemm();
-      } else if (fuse_r) {
+        if (body.fuse_r) mu_r_gemm();
+      } else if (body.fuse_r) {
         p_xir.launch(stream, 1.0, 0.0);  // {X^-1 = L^-T L^-1 | R = mu_p I - XY}
       } else {
         q_xinv.launch(stream, 1.0, 0.0);
       }
       return;
     }
-    if (fuse_r) mu_r_gemm();
+    if (body.fuse_r) mu_r_gemm();
     blk_lin(LX, X, 1.0, nullptr, 0.0);
     f_X.potrf(stream, info);
     if (lu_x()) {
@@ -2874,9 +2929,8 @@ struct Solver final : HandleBase {
     if constexpr (std::is_same<T, double>::value) {
       if (fast_schur) {
         if (!schur_fused) p_txy.launch(stream, 1.0, 0.0);
-        if (ty_ahead) {  // V^T Y came from the side stream
-          HIPCHK(hipStreamWaitEvent(stream, ev_ty, 0));
-          ty_ahead = false;
+        if (h_ty.armed()) {  // V^T Y came from the side stream
+          h_ty.join(stream);
         } else if (!(schur_fused && fused_y)) {
           p_ty.launch(stream, 1.0, 0.0);
         }
@@ -2931,12 +2985,9 @@ struct Solver final : HandleBase {
     factor_q();
   }
   // side_x21: X21 on the side stream (the loop body), joined before the first solve
-  bool w_split = false;  // the last factor_local ran W1's products on aux2 (ev_w recorded)
-  bool fuse_alpha = false;   // enqueue_iteration: STEP leaves alpha to UPDATE's launch
-  bool alpha_fused = false;  // STEP left it (the next st_update forms it)
   void factor_local(bool side_x21 = false) {
     s_lower = false;  // S now turns into L^-1 (or the LU factors)
-    w_split = false;
+    h_w.disarm();
     // (inner timing buckets: a mixed batch counts where most of its work is; the reference's
     // chol_S / CinvB / Q split, MPMP.jl:1429-1495)
     if (lu_sq()) {                            // approx_lu! (MPMP.jl:1433-1494)
@@ -2958,19 +3009,13 @@ struct Solver final : HandleBase {
       seg(CLRSDP_INNER_CINVB, [&] { f_a.launch(stream, 1.0, 0.0); });          // {L21^T | W}
       // W1 = L11^-1 B1, then W1^T W1 and B2' = B2 - L21 W1: beside the S22 chain in a loop body
       const bool split = side_x21 && nc2;
-      w_split = split;
       auto w_work = [&] {
         seg(CLRSDP_INNER_CINVB, [&] { f_w.launch(stream, 1.0, 0.0); });
         seg(CLRSDP_INNER_Q, [&] { f_w2.launch(stream, 1.0, 0.0); });
       };
       if (split) {
-        HIPCHK(hipEventRecord(ev_fa, stream));
-        HIPCHK(hipStreamWaitEvent(aux2, ev_fa, 0));
-        {
-          StreamSwitch on_aux2(stream, aux2);
-          w_work();
-        }
-        HIPCHK(hipEventRecord(ev_w, aux2));
+        fork(fev[EV_FA], aux2, w_work);
+        h_w.signal(aux2);
       } else {
         w_work();
       }
@@ -2982,25 +3027,20 @@ struct Solver final : HandleBase {
           // that the first side stream is free for the right-hand side and chol(Q) as soon as Q
           // is summed
           const hipStream_t xs = split ? aux2 : aux;
-          const hipStream_t main_s = stream;
-          HIPCHK(hipEventRecord(ev_x2, main_s));
-          HIPCHK(hipStreamWaitEvent(xs, ev_x2, 0));
-          {
-            StreamSwitch on_side(stream, xs);  // restored on scope exit, also when a launch throws
+          fork(fev[EV_X2], xs, [&] {
             seg(CLRSDP_INNER_CHOL_S, [&] {
-              f_x1.launch(xs, 1.0, 0.0);
-              f_x2.launch(xs, -1.0, 0.0);
+              f_x1.launch(stream, 1.0, 0.0);
+              f_x2.launch(stream, -1.0, 0.0);
             });
-          }
-          HIPCHK(hipEventRecord(ev_x21, xs));
-          pending_x21 = true;
+          });
+          h_x21.signal(xs);
         } else {
           seg(CLRSDP_INNER_CHOL_S, [&] {
             f_x1.launch(stream, 1.0, 0.0);
             f_x2.launch(stream, -1.0, 0.0);
           });
         }
-        if (split) HIPCHK(hipStreamWaitEvent(stream, ev_w, 0));
+        h_w.wait(stream);  // (stays armed: the loop body's side stream joins it too)
         seg(CLRSDP_INNER_CINVB, [&] { f_c.launch(stream, 1.0, 0.0); });
         seg(CLRSDP_INNER_Q, [&] { f_d.launch(stream, 1.0, 1.0); });
       }
@@ -3015,13 +3055,10 @@ struct Solver final : HandleBase {
       if (s_split) {  // L_j^-1 for the GEMV solves, beside W_j and the Q chain
         const hipStream_t ls = side_x21 && aux2 ? aux2 : stream;  // (a loop body only)
         if (ls != stream) {
-          HIPCHK(hipEventRecord(ev_sp, stream));
-          HIPCHK(hipStreamWaitEvent(ls, ev_sp, 0));
-        }
-        t_Sinv.launch(ls, false);
-        if (ls != stream) {
-          HIPCHK(hipEventRecord(ev_sinv, ls));
-          pending_sinv = true;
+          fork(fev[EV_SP], ls, [&] { t_Sinv.launch(stream, false); });
+          h_sinv.signal(ls);
+        } else {
+          t_Sinv.launch(stream, false);
         }
       }
       seg(CLRSDP_INNER_CINVB, [&] {
@@ -3041,14 +3078,23 @@ struct Solver final : HandleBase {
     // critical path)
     T* q_dual = !reg_Q && Qf ? Qf : nullptr;
     qf_fresh = q_dual != nullptr;
-    if (world == 1 && nc()) {
-      launch_slab_sum4<T>(stream, Qslab, nc(), q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
-    } else {
-      if (nc()) launch_slab_sum4<T>(stream, Qslab, nc(), q2, q2, xsend);
-      else fill(xsend, 0.0, q2);
-      exchange(2, q2);
-      launch_slab_sum4<T>(stream, xrecv, world, q2, q2, Q, nullptr, 0.0, 1.0, q_dual);
-    }
+    gather_sum(Qslab, nc(), q2, 2, Q, nullptr, 0.0, 1.0, q_dual);
+  }
+  // The sum over all clusters of `cnt` local slabs of n numbers each (stride n): where to read it.
+  // One rank with slabs: the slabs themselves; otherwise this rank's sum (zeros without slabs)
+  // is all-gathered and the slabs are the ranks' sums in xrecv.
+  std::pair<const T*, int> gather_slabs(const T* slabs, int cnt, int64_t n, int tag) {
+    if (world == 1 && cnt) return {slabs, cnt};
+    if (cnt) launch_slab_sum4<T>(stream, slabs, cnt, n, n, xsend);
+    else fill(xsend, 0.0, n);
+    exchange(tag, n);
+    return {xrecv, world};
+  }
+  // out = cbase * base + csum * (that sum), out2 (if any) the same: one launch at one rank
+  void gather_sum(const T* slabs, int cnt, int64_t n, int tag, T* out, const T* base = nullptr,
+                  double cbase = 0.0, double csum = 1.0, T* out2 = nullptr) {
+    const auto [src, k] = gather_slabs(slabs, cnt, n, tag);
+    launch_slab_sum4<T>(stream, src, k, n, n, out, base, cbase, csum, out2);
   }
   void factor_q() {
     seg(CLRSDP_INNER_CHOL_Q, [&] { factor_q_(); });
@@ -3111,7 +3157,7 @@ struct Solver final : HandleBase {
   void residuals_finish(bool defer = false) {
     const int64_t k = n_y + 2;
     if (world == 1 && nc()) {  // p = b - sum_j B_j^T x_j in one launch; maxima folded
-      launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, pvec, bvec, 1.0, -1.0);
+      gather_sum(pslab, nc(), n_y, 3, pvec, bvec, 1.0, -1.0);
       fold(tmpsc, 1, 2, SC_ERR_PMAT);
       fold(tmpsc + 1, 1, 2, SC_ERR_DVEC);
       fold(pvec, (int)n_y, 4, SC_ERR_PVEC);
@@ -3171,20 +3217,19 @@ struct Solver final : HandleBase {
     seg(CLRSDP_INNER_SOLVE, [&] { direction_solves(tag); });
     // dX = P + sum_i dx_i A_i
     seg(CLRSDP_INNER_DX, [&] { weighted_A(dx, p_wA_dX, dX, 1.0); });
-    if (tag == 6 && xy_ov_body && xy_ov_ok) {
+    if (tag == 6 && body.xy_ov_body && xy_ov_ok) {
       // the X step length beside dY and the Y one (STEP joins it)
-      HIPCHK(hipEventRecord(ev_dxo, stream));
-      HIPCHK(hipStreamWaitEvent(aux, ev_dxo, 0));
-      c_stepX.launch(aux, 1.0, 0.0);
-      e_Xs.eigmin(aux, eigX);
-      HIPCHK(hipEventRecord(ev_stx, aux));
-      xy_ov = true;
+      fork(fev[EV_DXO], aux, [&] {
+        c_stepX.launch(stream, 1.0, 0.0);
+        e_Xs.eigmin(stream, eigX);
+      });
+      h_stx.signal(aux);
     }
     // dY = sym(X^-1 (R - dX Y))
     seg(CLRSDP_INNER_DY, [&] {
       if (c_dY.on) {
-        dy_dot_ready = dy_dot_ok && tag == 4;
-        c_dY.u.dot_part = dy_dot_ready ? reinterpret_cast<double*>(dotp) : nullptr;
+        body.dy_dot_ready = dy_dot_ok && tag == 4;
+        c_dY.u.dot_part = body.dy_dot_ready ? reinterpret_cast<double*>(dotp) : nullptr;
         c_dY.launch(stream, -1.0, 1.0);
       } else {
         p_dXY.launch(stream, -1.0, 1.0);
@@ -3194,19 +3239,12 @@ struct Solver final : HandleBase {
     });
   }
   // t_j = L_j^-1 rhs_j and the slabs W_j^T t_j: the part of the batched solve that needs no Q^-1
-  // (it waits for X21 / L_j^-1 where a side stream produced them).  head_ahead: the loop body has
-  // run it on the side stream already, beside chol(Q)
-  bool head_ahead = false;
+  // (it waits for X21 / L_j^-1 where a side stream produced them).  body.head_ahead: the loop body
+  // has run it on the side stream already, beside chol(Q)
   bool qchol_main = !env_off("CLRSDP_QCHOL_MAIN");
   void solve_head() {
-    if (pending_x21) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_x21, 0));
-      pending_x21 = false;
-    }
-    if (pending_sinv) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_sinv, 0));
-      pending_sinv = false;
-    }
+    h_x21.join(stream);
+    h_sinv.join(stream);
     if (reg_S) {
       q_t.launch(stream, 1.0, 0.0);
     } else if (s_split) {
@@ -3220,10 +3258,7 @@ struct Solver final : HandleBase {
   // the three-stage solve and dx as separate batched launches (any word type / rank count)
   void direction_solves(int tag) {
     // t_j = L_j^-1 rhs_j ;  u = sum_j W_j^T t_j ;  dy = Q^-1 (p - u) ; dx_j = L_j^-T (t_j + W_j dy)
-    if (pending_x21) {  // X21 (lower-left block of L^-1) comes from the side stream
-      HIPCHK(hipStreamWaitEvent(stream, ev_x21, 0));
-      pending_x21 = false;
-    }
+    h_x21.join(stream);  // X21 (lower-left block of L^-1) comes from the side stream
     if (lu_sq()) {
       direction_solves_lu(tag);
       return;
@@ -3232,25 +3267,15 @@ struct Solver final : HandleBase {
       if (cls_on) {  // t and the partial slabs | dy = Q^-1 (p - sum) | u and dx: three launches
         const unsigned g = (unsigned)(nc() * cls_nrb);
         cl_solve_t<<<g, 256, 0, stream>>>(d_cls, cls_nrb, (int)n_y, pslab);
-        const double* src = pslab;
-        int cnt = nc() * cls_nrb;
-        if (world > 1) {
-          launch_slab_sum4<T>(stream, pslab, cnt, n_y, n_y, xsend);
-          exchange(tag, n_y);
-          src = xrecv;
-          cnt = world;
-        }
-        if (pending_q) {
-          HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
-          pending_q = false;
-        }
+        const auto [src, cnt] = gather_slabs(pslab, nc() * cls_nrb, n_y, tag);  // (cls_on: nc() > 0)
+        h_q.join(stream);
         launch_slab_qsolve(stream, src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
         cl_solve_dx<<<g, 256, 0, stream>>>(d_cls, cls_nrb, (int)n_y, dyv);
         HIPCHK(hipGetLastError());
         return;
       }
     }
-    if (head_ahead) head_ahead = false;  // (the loop body ran it on the side stream, beside chol(Q))
+    if (body.head_ahead) body.head_ahead = false;  // (the loop body ran it on the side stream, beside chol(Q))
     else solve_head();
     // fp64 with the explicit Q^-1: r = p - sum of the slabs and dy = Q^-1 r in one launch
     // (slab_qsolve)
@@ -3262,19 +3287,8 @@ struct Solver final : HandleBase {
       const long long cnt_x = (world == 1 && nc()) ? nc() : world;
       const bool small_sum = (long long)cdiv(n_y, 64) * cnt_x * n_y <= (1LL << 20);
       if (reg_Q && small_sum && lds <= 64 * 1024) {
-        const double* src = pslab;
-        int cnt = nc();
-        if (!(world == 1 && nc())) {
-          if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
-          else fill(xsend, 0.0, n_y);
-          exchange(tag, n_y);
-          src = xrecv;
-          cnt = world;
-        }
-        if (pending_q) {
-          HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
-          pending_q = false;
-        }
+        const auto [src, cnt] = gather_slabs(pslab, nc(), n_y, tag);
+        h_q.join(stream);
         launch_slab_qsolve(stream, src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
         HIPCHK(hipGetLastError());
         fused_done = true;
@@ -3283,18 +3297,8 @@ struct Solver final : HandleBase {
     if (!fused_done) {
       // r = p - sum_j W_j^T t_j  (-> uvec with the explicit Q^-1, -> dyv for the two solves)
       T* rv = (reg_Q || q_split) ? uvec : dyv;
-      if (world == 1 && nc()) {  // one launch
-        launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, rv, pvec, 1.0, -1.0);
-      } else {
-        if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
-        else fill(xsend, 0.0, n_y);
-        exchange(tag, n_y);
-        launch_slab_sum4<T>(stream, xrecv, world, n_y, n_y, rv, pvec, 1.0, -1.0);
-      }
-      if (pending_q) {  // L_Q^-1 and Q^-1 are being computed on the side stream (iterate)
-        HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
-        pending_q = false;
-      }
+      gather_sum(pslab, nc(), n_y, tag, rv, pvec, 1.0, -1.0);
+      h_q.join(stream);  // L_Q^-1 and Q^-1 are being computed on the side stream (iterate)
       if (reg_Q || q_split) {
         q_qdy.launch(stream, 1.0, 0.0);         // dy = Q^-1 r
       } else {
@@ -3317,18 +3321,8 @@ struct Solver final : HandleBase {
     pm_rhs.launch(stream);                    // t_j = rhs_j[perm_j]
     tl_t.launch(stream, false);               // t_j = L_j^-1 t_j
     lq_Wt.launch(stream, 1.0, 0.0);           // slab_j = W2_j^T t_j  (B_j^T U_j^-1 t_j)
-    if (world == 1 && nc()) {
-      launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, uvec, pvec, 1.0, -1.0);
-    } else {
-      if (nc()) launch_slab_sum4<T>(stream, pslab, nc(), n_y, n_y, xsend);
-      else fill(xsend, 0.0, n_y);
-      exchange(tag, n_y);
-      launch_slab_sum4<T>(stream, xrecv, world, n_y, n_y, uvec, pvec, 1.0, -1.0);
-    }
-    if (pending_q) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
-      pending_q = false;
-    }
+    gather_sum(pslab, nc(), n_y, tag, uvec, pvec, 1.0, -1.0);
+    h_q.join(stream);
     pm_r.launch(stream);                      // dy = (p - u)[perm_Q]
     tl_Q1.launch(stream, false);              // L_Q^-1
     tl_Q2.launch(stream, true);               // U_Q^-1
@@ -3336,9 +3330,9 @@ struct Solver final : HandleBase {
     tl_dx.launch(stream, true);               // dx_j = U_j^-1 (.)
   }
   void st_corrector_r(const clrsdp_params* prm, int pd_feas) {
-    if (dy_dot_ready) fold(dotp, dy_dot_cnt, 0, SC_DOT_XDY);  // (from the predictor's dY chain)
+    if (body.dy_dot_ready) fold(dotp, dy_dot_cnt, 0, SC_DOT_XDY);  // (from the predictor's dY chain)
     else blk_dot(X, Y, dX, dY, 1, SC_DOT_XDY, 5);
-    dy_dot_ready = false;
+    body.dy_dot_ready = false;
     scalars(prm, pd_feas, 1);
     if constexpr (std::is_same<T, double>::value) {
       // R still holds mu_p I - XY from MU_R (the predictor only reads it), so one GEMM:
@@ -3352,11 +3346,10 @@ struct Solver final : HandleBase {
   void st_step(const clrsdp_params* prm, int pd_feas) {
     if (reg_blk) {
       // L_X^-1, L_Y^-1 from the X^-1 stage;  M = L^-1 dM L^-T on MFMA; one eigen launch
-      if (xy_ov) {  // (the X half is on the side stream since dX)
+      if (h_stx.armed()) {  // (the X half is on the side stream since dX)
         c_stepY.launch(stream, 1.0, 0.0);
         e_Ys.eigmin(stream, eigY);
-        HIPCHK(hipStreamWaitEvent(stream, ev_stx, 0));
-        xy_ov = false;
+        h_stx.join(stream);
       } else {
         if (c_step.on) {
           c_step.launch(stream, 1.0, 0.0);        // X and Y blocks together, one launch
@@ -3382,10 +3375,10 @@ struct Solver final : HandleBase {
       t_sY2.launch(stream, false);
       e_Y.eigmin(stream, eigY);
     }
-    if (world == 1 && nb() && fuse_alpha) {
+    if (world == 1 && nb() && body.fuse_alpha) {
       // (a loop body: the minima and alpha are formed by UPDATE's update_state, one launch less)
       flush_scalars();
-      alpha_fused = true;
+      body.alpha_fused = true;
       return;
     }
     if (world == 1 && nb()) {  // min over the blocks straight into the scalar slots
@@ -3431,7 +3424,7 @@ struct Solver final : HandleBase {
     // one launch updates x, y, X, Y (guarded by the status words: no update after a failed
     // factorisation) and leaves the partial sums <X,Y> (next MU_R), <c,x> and <b,y>
     StepAlpha<T> sa{};
-    if (alpha_fused) {
+    if (body.alpha_fused) {
       sa.eigX = eigX;
       sa.eigY = eigY;
       sa.nb = nb();
@@ -3443,7 +3436,7 @@ struct Solver final : HandleBase {
       sa.sap = SC_ALPHA_P;
       sa.sad = SC_ALPHA_D;
       sa.pdslot = SC_PDFEAS;
-      alpha_fused = false;
+      body.alpha_fused = false;
     }
     launch_update_state<T>(stream, X, dX, Y, dY, nblk_el, x, dx, nx, cvec, y, dyv, n_y, bvec,
                            sc + SC_ALPHA_P, sc + SC_ALPHA_D, info, info_count, upart, sa);
@@ -3585,41 +3578,34 @@ struct Solver final : HandleBase {
     //   after FACTOR's Q sum: chol(Q) -> L_Q^-1, Q^-1 -- or, with q_main below, p, the guarded
     //                copy and the head of the predictor's solve while the main stream factors Q
     const hipStream_t main_s = stream;
-    auto side = [&](hipEvent_t ev, auto&& work) {
-      HIPCHK(hipEventRecord(ev, main_s));
-      HIPCHK(hipStreamWaitEvent(aux, ev, 0));
-      StreamSwitch on_aux(stream, aux);
-      work();
-    };
-    fuse_r = std::is_same<T, double>::value && timing != 1 && !p_xir.h.empty();
+    body.fuse_r = std::is_same<T, double>::value && timing != 1 && !p_xir.h.empty();
     mark(CLRSDP_STAGE_MU_R);
     stage(CLRSDP_STAGE_MU_R, prm, pd_feas);
     // V^T Y of the Schur stage only needs the state: it runs beside chol_inv(X, Y), which leaves
-    // half the CUs idle, and SCHUR waits for it (ev_ty) before the pairs launch
+    // half the CUs idle, and SCHUR waits for it (h_ty) before the pairs launch
     const bool ty_side = fast_schur && !p_ty.h.empty() && !(schur_fused && fused_y);
     // P = sum x_i A_i - X - C is first read by the side stream's Z after SCHUR: enqueued there
     // (one fork of the critical path fewer) unless V^T Y needs the fork anyway
     const bool p_late = !ty_side;
     if (!p_late)
-      side(ev_m, [&] {
+      fork(fev[EV_M], aux, [&] {
         if (ty_side) {
           p_ty.launch(stream, 1.0, 0.0);
-          HIPCHK(hipEventRecord(ev_ty, stream));
-          ty_ahead = true;
+          h_ty.signal(stream);
         }
         residuals_P();
       });
     mark(CLRSDP_STAGE_XINV);
     stage(CLRSDP_STAGE_XINV, prm, pd_feas);
-    fuse_r = false;
+    body.fuse_r = false;
     mark(CLRSDP_STAGE_SCHUR);
     stage(CLRSDP_STAGE_SCHUR, prm, pd_feas);
     // (Z waits for SCHUR although it could start after XINV: beside the MFMA-bound Schur
     // products it only slowed them down, beside FACTOR's latency-bound factorisations it is free)
     // The predictor's Z first (its MFMA chain fills the CUs that chol(S11) leaves idle), then the
     // residuals; the right-hand side (U = Z V and its column sums) after FACTOR's side products
-    // W1^T W1 and B2' (ev_w), which are on the critical path to W2 = L22^-1 B2'
-    side(ev_s, [&] {
+    // W1^T W1 and B2' (h_w), which are on the critical path to W2 = L22^-1 B2'
+    fork(fev[EV_S], aux, [&] {
       if (p_late) residuals_P();
       direction_Z();
       residuals_rest(true);
@@ -3637,39 +3623,34 @@ struct Solver final : HandleBase {
     const bool q_main = qchol_main && std::is_same<T, double>::value && world == 1 && timing != 1 &&
                         nc() && !lu_sq() && !cls_on;
     {
-      if (w_split) HIPCHK(hipStreamWaitEvent(aux, ev_w, 0));
+      h_w.join(aux);
       StreamSwitch on_aux(stream, aux);
       direction_rhs();
-      if (!q_main) HIPCHK(hipEventRecord(ev_r, aux));
+      if (!q_main) HIPCHK(hipEventRecord(fev[EV_R], aux));
     }
-    HIPCHK(hipEventRecord(ev_qa, main_s));
-    HIPCHK(hipStreamWaitEvent(aux, ev_qa, 0));
     if (q_main) {
+      fork(fev[EV_QA], aux, [] {});  // (the side stream goes on below, once Q is being factored)
       factor_q();
       if (capturing && inject_capture_fail)
         throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
       {
-        // (behind ev_qa: W, L^-1 and the halt word come from the main stream)
+        // (behind EV_QA: W, L^-1 and the halt word come from the main stream)
         StreamSwitch on_aux(stream, aux);
         residuals_finish(true);
         if (keep_res) copy_guarded(pres, pvec, n_y);
         solve_head();
-        head_ahead = true;
-        HIPCHK(hipEventRecord(ev_r, aux));
+        body.head_ahead = true;
+        HIPCHK(hipEventRecord(fev[EV_R], aux));
       }
-      HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
+      HIPCHK(hipStreamWaitEvent(main_s, fev[EV_R], 0));
     } else {
       // side stream: chol(Q) -> L_Q^-1, waited for just before the first Q solve
-      {
-        StreamSwitch on_aux(stream, aux);
-        factor_q();
-      }
-      HIPCHK(hipEventRecord(ev_q, aux));
-      pending_q = true;
+      fork(fev[EV_QA], aux, [&] { factor_q(); });
+      h_q.signal(aux);
       if (capturing && inject_capture_fail)
         throw ClrsdpError{CLRSDP_E_HIP, "injected capture failure (CLRSDP_INJECT_CAPTURE_FAIL)"};
       mark(CLRSDP_STAGE_RESIDUALS);
-      HIPCHK(hipStreamWaitEvent(main_s, ev_r, 0));
+      HIPCHK(hipStreamWaitEvent(main_s, fev[EV_R], 0));
       residuals_finish(timing != 1);
       if (keep_res) copy_guarded(pres, pvec, n_y);
     }
@@ -3678,30 +3659,16 @@ struct Solver final : HandleBase {
     direction_rest(4);   // Z, U and rhs came from the side stream
     // (STEP's alpha is formed inside UPDATE's launch; the per-stage timing mode keeps the scalar
     // launch so STEP's time includes alpha)
-    fuse_alpha = timing != 1;
-    xy_ov_body = timing != 1;
+    body.fuse_alpha = timing != 1;
+    body.xy_ov_body = timing != 1;
     for (int s = CLRSDP_STAGE_CORRECTOR_R; s < CLRSDP_NUM_STAGES; ++s) {
       mark(s);
       stage(s, prm, pd_feas);
     }
-    fuse_alpha = false;
-    xy_ov_body = false;
-    if (xy_ov) {  // (STEP did not run: join the side stream anyway)
-      HIPCHK(hipStreamWaitEvent(stream, ev_stx, 0));
-      xy_ov = false;
-    }
-    if (pending_q) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_q, 0));
-      pending_q = false;
-    }
-    if (pending_x21) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_x21, 0));
-      pending_x21 = false;
-    }
-    if (pending_sinv) {
-      HIPCHK(hipStreamWaitEvent(stream, ev_sinv, 0));
-      pending_sinv = false;
-    }
+    body.fuse_alpha = false;
+    body.xy_ov_body = false;
+    // whatever no stage joined (a hand-off whose consumer did not run) joins the main stream here
+    for (Handoff* h : handoffs) h->join(stream);
     if (timing == 1) HIPCHK(hipEventRecord(ev[CLRSDP_NUM_STAGES], stream));
   }
 
@@ -3762,10 +3729,10 @@ struct Solver final : HandleBase {
         capturing = false;
         // join the side stream (it may have been forked into the capture) so that the capture
         // ends cleanly and the streams stay usable
-        if (hipEventRecord(ev_join, aux) == hipSuccess)
-          (void)hipStreamWaitEvent(stream, ev_join, 0);
-        if (hipEventRecord(ev_join2, aux2) == hipSuccess)
-          (void)hipStreamWaitEvent(stream, ev_join2, 0);
+        if (hipEventRecord(fev[EV_JOIN], aux) == hipSuccess)
+          (void)hipStreamWaitEvent(stream, fev[EV_JOIN], 0);
+        if (hipEventRecord(fev[EV_JOIN2], aux2) == hipSuccess)
+          (void)hipStreamWaitEvent(stream, fev[EV_JOIN2], 0);
         (void)hipStreamEndCapture(stream, &graph);
         if (graph) (void)hipGraphDestroy(graph);
         (void)hipGetLastError();
@@ -3791,15 +3758,8 @@ struct Solver final : HandleBase {
   // the per-body enqueue state a failed (partial) capture may have left set; an eager re-enqueue
   // must not wait on events recorded only inside the aborted capture
   void reset_body_state() {
-    pending_q = pending_x21 = pending_sinv = false;
-    ty_ahead = false;
-    w_split = false;
-    head_ahead = false;
-    dy_dot_ready = false;
-    alpha_fused = false;
-    fuse_alpha = false;
-    fuse_r = false;
-    xy_ov_body = xy_ov = false;
+    body = {};
+    for (Handoff* h : handoffs) h->disarm();
   }
   void launch_graph_or_eager(const clrsdp_params* prm, int pd_feas) {
     if (world == 1 && !inject_capture_fail) {
@@ -3902,7 +3862,7 @@ struct Solver final : HandleBase {
     snapped = true;
   }
   void restore_state() override {
-    dy_dot_ready = false;
+    body.dy_dot_ready = false;
     if (!snapped) throw ClrsdpError{CLRSDP_E_STATE, "restore_state without save_state"};
     snap_copy(false);
     refresh_xy_part();
@@ -4069,164 +4029,12 @@ struct DevBuf {
     return q;
   }
 };
-
-// lambda_min of each symmetric block at the word type T (the eigenvalue part of
-// compute_step_length, MPMP.jl:1857-1870): planes in, planes out
-template <class T>
-void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, double* ep) {
-  constexpr int W = Num<T>::W;
-  DeviceGuard dg(device);
-  std::vector<int64_t> off(nblk + 1, 0);
-  for (int64_t b = 0; b < nblk; ++b) {
-    if (n[b] <= 0 || n[b] > 4096) throw ClrsdpError{CLRSDP_E_ARG, "block size out of range"};
-    off[b + 1] = off[b] + n[b] * n[b];
-  }
-  const int64_t tot = off[nblk];
-  // planes -> interleaved limbs (the layout of T)
-  std::vector<double> h((size_t)tot * W);
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
-  DevBuf mem;
-  T* A = mem.alloc<T>(tot);
-  T* eig = mem.alloc<T>(nblk);
-  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
-  MatPlan<T> eg;
-  for (int64_t b = 0; b < nblk; ++b) eg.add(A + off[b], (int)n[b], (int)n[b]);
-  eg.finalize(MatPlan<T>::Use::EIG_ONLY);
+// the stream a stand-alone entry launches on
+struct StreamOwner {
   hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  eg.eigmin(s, eig);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));
-  std::vector<double> he((size_t)nblk * W);
-  HIPCHK(hipMemcpy(he.data(), eig, (size_t)nblk * sizeof(T), hipMemcpyDeviceToHost));
-  for (int64_t b = 0; b < nblk; ++b)
-    for (int q = 0; q < W; ++q) ep[(size_t)q * nblk + b] = he[(size_t)b * W + q];
-}
-
-// Pivoted LU of each block at the word type T through LuPlan, as the solver's LU path runs it
-// (getrf_batched, or the blocked chain beyond its panel / with CLRSDP_LU_BLK=1): planes in and out
-template <class T>
-void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t* perm, int32_t* info) {
-  constexpr int W = Num<T>::W;
-  std::vector<int64_t> off(nblk + 1, 0), poff(nblk + 1, 0);
-  for (int64_t b = 0; b < nblk; ++b) {
-    off[b + 1] = off[b] + n[b] * n[b];
-    poff[b + 1] = poff[b] + n[b];
-  }
-  DeviceGuard dg(device);
-  const int64_t tot = off[nblk], np = poff[nblk];
-  std::vector<double> h((size_t)tot * W);
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
-  DevBuf mem;
-  T* A = mem.alloc<T>(tot);
-  int* dperm = mem.alloc<int>(np);
-  int* dinfo = mem.alloc<int>(nblk);
-  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
-  LuPlan<T> lu;
-  for (int64_t b = 0; b < nblk; ++b) lu.add(A + off[b], dperm + poff[b], (int)n[b], (int)n[b]);
-  lu.finalize();
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  lu.launch(s, dinfo);
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemcpy(h.data(), A, (size_t)tot * sizeof(T), hipMemcpyDeviceToHost));
-  static_assert(sizeof(int) == sizeof(int32_t), "perm and info are 32-bit");
-  HIPCHK(hipMemcpy(perm, dperm, (size_t)np * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
-}
-
-// Cholesky factor of each block at the word type T, as the solver runs it: in place through
-// MatPlan::potrf (inverse = 0), or L^-1 through CholInvPlan into a buffer of its own that holds
-// NaN bytes before the launch, so every entry that comes back was written by the kernel
-// (inverse = 1); planes in and out
-template <class T>
-void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double* Ap, int32_t* info) {
-  constexpr int W = Num<T>::W;
-  std::vector<int64_t> off(nblk + 1, 0);
-  for (int64_t b = 0; b < nblk; ++b) off[b + 1] = off[b] + n[b] * n[b];
-  DeviceGuard dg(device);
-  // potrf_batched's size bound (E_ARG) before any buffer is allocated or copied; fac.finalize()
-  // below makes the same comparison again, on the cached figure
-  if (!inverse) MatPlan<T>::check_potrf((int)*std::max_element(n, n + nblk));
-  const int64_t tot = off[nblk];
-  std::vector<double> h((size_t)tot * W);
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
-  DevBuf mem;
-  T* A = mem.alloc<T>(tot);
-  T* X = inverse ? mem.alloc<T>(tot) : nullptr;
-  int* dinfo = mem.alloc<int>(nblk);
-  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
-  MatPlan<T> fac;
-  CholInvPlan<T> ci;
-  for (int64_t b = 0; b < nblk; ++b) {
-    if (inverse) ci.add(A + off[b], (int)n[b], (int)n[b], X + off[b], (int)n[b]);
-    else fac.add(A + off[b], (int)n[b], (int)n[b]);
-  }
-  fac.finalize();
-  ci.finalize();
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  if (inverse) {
-    HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)tot * sizeof(T), s));
-    ci.launch(s, dinfo);
-  } else {
-    fac.potrf(s, dinfo);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemcpy(h.data(), inverse ? X : A, (size_t)tot * sizeof(T), hipMemcpyDeviceToHost));
-  static_assert(sizeof(int) == sizeof(int32_t), "info is 32-bit");
-  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) Ap[(size_t)q * tot + e] = h[(size_t)e * W + q];
-}
-
-// Triangular solves of each block at the word type T through TrsmPlan, as the solver runs them
-// (trsv_wave / trsm_batched, or the blocked chain beyond the on-chip panel / with
-// CLRSDP_TRSM_BLK=1): planes in, B planes in and out
-template <class T>
-void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n, const int64_t* nrhs,
-                const double* Ap, double* Bp) {
-  constexpr int W = Num<T>::W;
-  std::vector<int64_t> off(nblk + 1, 0), boff(nblk + 1, 0);
-  for (int64_t b = 0; b < nblk; ++b) {
-    off[b + 1] = off[b] + n[b] * n[b];
-    boff[b + 1] = boff[b] + n[b] * nrhs[b];
-  }
-  DeviceGuard dg(device);
-  const int64_t tot = off[nblk], totb = boff[nblk];
-  std::vector<double> h((size_t)tot * W), hb((size_t)totb * W);
-  for (int64_t e = 0; e < tot; ++e)
-    for (int q = 0; q < W; ++q) h[(size_t)e * W + q] = Ap[(size_t)q * tot + e];
-  for (int64_t e = 0; e < totb; ++e)
-    for (int q = 0; q < W; ++q) hb[(size_t)e * W + q] = Bp[(size_t)q * totb + e];
-  DevBuf mem;
-  T* A = mem.alloc<T>(tot);
-  T* B = mem.alloc<T>(totb);
-  HIPCHK(hipMemcpy(A, h.data(), (size_t)tot * sizeof(T), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(B, hb.data(), (size_t)totb * sizeof(T), hipMemcpyHostToDevice));
-  TrsmPlan<T> tp;
-  tp.mode = mode;
-  for (int64_t b = 0; b < nblk; ++b)
-    tp.add(A + off[b], (int)n[b], B + boff[b], (int)n[b], (int)n[b], (int)nrhs[b]);
-  tp.finalize();
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  tp.launch(s, trans != 0);
-  HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemcpy(hb.data(), B, (size_t)totb * sizeof(T), hipMemcpyDeviceToHost));
-  for (int64_t e = 0; e < totb; ++e)
-    for (int q = 0; q < W; ++q) Bp[(size_t)q * totb + e] = hb[(size_t)e * W + q];
-}
+  StreamOwner() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ~StreamOwner() { (void)hipStreamDestroy(s); }
+};
 
 // planes of an arena of `cnt` numbers <-> the interleaved limbs of T (bit copies: a NaN keeps
 // its payload)
@@ -4254,6 +4062,122 @@ void download_planes(const T* d, double* planes, int64_t cnt) {
   for (int q = 0; q < W; ++q)
     for (int64_t e = 0; e < cnt; ++e)
       std::memcpy(&planes[(size_t)q * cnt + e], &h[(size_t)e * W + q], sizeof(double));
+}
+
+// lambda_min of each symmetric block at the word type T (the eigenvalue part of
+// compute_step_length, MPMP.jl:1857-1870): planes in, planes out
+template <class T>
+void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, double* ep) {
+  DeviceGuard dg(device);
+  std::vector<int64_t> off(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    if (n[b] <= 0 || n[b] > 4096) throw ClrsdpError{CLRSDP_E_ARG, "block size out of range"};
+    off[b + 1] = off[b] + n[b] * n[b];
+  }
+  DevBuf mem;
+  T* A = upload_planes<T>(mem, Ap, off[nblk]);
+  T* eig = mem.alloc<T>(nblk);
+  MatPlan<T> eg;
+  for (int64_t b = 0; b < nblk; ++b) eg.add(A + off[b], (int)n[b], (int)n[b]);
+  eg.finalize(MatPlan<T>::Use::EIG_ONLY);
+  StreamOwner so;
+  eg.eigmin(so.s, eig);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  download_planes<T>(eig, ep, nblk);
+}
+
+// Pivoted LU of each block at the word type T through LuPlan, as the solver's LU path runs it
+// (getrf_batched, or the blocked chain beyond its panel / with CLRSDP_LU_BLK=1): planes in and out
+template <class T>
+void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t* perm, int32_t* info) {
+  std::vector<int64_t> off(nblk + 1, 0), poff(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    off[b + 1] = off[b] + n[b] * n[b];
+    poff[b + 1] = poff[b] + n[b];
+  }
+  DeviceGuard dg(device);
+  const int64_t tot = off[nblk], np = poff[nblk];
+  DevBuf mem;
+  T* A = upload_planes<T>(mem, Ap, tot);
+  int* dperm = mem.alloc<int>(np);
+  int* dinfo = mem.alloc<int>(nblk);
+  LuPlan<T> lu;
+  for (int64_t b = 0; b < nblk; ++b) lu.add(A + off[b], dperm + poff[b], (int)n[b], (int)n[b]);
+  lu.finalize();
+  StreamOwner so;
+  lu.launch(so.s, dinfo);
+  HIPCHK(hipStreamSynchronize(so.s));
+  static_assert(sizeof(int) == sizeof(int32_t), "perm and info are 32-bit");
+  HIPCHK(hipMemcpy(perm, dperm, (size_t)np * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  download_planes<T>(A, Ap, tot);
+}
+
+// Cholesky factor of each block at the word type T, as the solver runs it: in place through
+// MatPlan::potrf (inverse = 0), or L^-1 through CholInvPlan into a buffer of its own that holds
+// NaN bytes before the launch, so every entry that comes back was written by the kernel
+// (inverse = 1); planes in and out
+template <class T>
+void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double* Ap, int32_t* info) {
+  std::vector<int64_t> off(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) off[b + 1] = off[b] + n[b] * n[b];
+  DeviceGuard dg(device);
+  // potrf_batched's size bound (E_ARG) before any buffer is allocated or copied; fac.finalize()
+  // below makes the same comparison again, on the cached figure
+  if (!inverse) MatPlan<T>::check_potrf((int)*std::max_element(n, n + nblk));
+  const int64_t tot = off[nblk];
+  DevBuf mem;
+  T* A = upload_planes<T>(mem, Ap, tot);
+  T* X = inverse ? mem.alloc<T>(tot) : nullptr;
+  int* dinfo = mem.alloc<int>(nblk);
+  MatPlan<T> fac;
+  CholInvPlan<T> ci;
+  for (int64_t b = 0; b < nblk; ++b) {
+    if (inverse) ci.add(A + off[b], (int)n[b], (int)n[b], X + off[b], (int)n[b]);
+    else fac.add(A + off[b], (int)n[b], (int)n[b]);
+  }
+  fac.finalize();
+  ci.finalize();
+  StreamOwner so;
+  if (inverse) {
+    HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)tot * sizeof(T), so.s));
+    ci.launch(so.s, dinfo);
+  } else {
+    fac.potrf(so.s, dinfo);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  static_assert(sizeof(int) == sizeof(int32_t), "info is 32-bit");
+  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  download_planes<T>(inverse ? X : A, Ap, tot);
+}
+
+// Triangular solves of each block at the word type T through TrsmPlan, as the solver runs them
+// (trsv_wave / trsm_batched, or the blocked chain beyond the on-chip panel / with
+// CLRSDP_TRSM_BLK=1): planes in, B planes in and out
+template <class T>
+void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n, const int64_t* nrhs,
+                const double* Ap, double* Bp) {
+  std::vector<int64_t> off(nblk + 1, 0), boff(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    off[b + 1] = off[b] + n[b] * n[b];
+    boff[b + 1] = boff[b] + n[b] * nrhs[b];
+  }
+  DeviceGuard dg(device);
+  const int64_t tot = off[nblk], totb = boff[nblk];
+  DevBuf mem;
+  T* A = upload_planes<T>(mem, Ap, tot);
+  T* B = upload_planes<T>(mem, Bp, totb);
+  TrsmPlan<T> tp;
+  tp.mode = mode;
+  for (int64_t b = 0; b < nblk; ++b)
+    tp.add(A + off[b], (int)n[b], B + boff[b], (int)n[b], (int)n[b], (int)nrhs[b]);
+  tp.finalize();
+  StreamOwner so;
+  tp.launch(so.s, trans != 0);
+  HIPCHK(hipStreamSynchronize(so.s));
+  download_planes<T>(B, Bp, totb);
 }
 
 // the arguments of clrsdp_gemm, checked by the caller (gemm_check)
@@ -4314,12 +4238,10 @@ int gemm_words(int device, const GemmCall& c) {
     }
   }
   g.finalize();
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  g.launch(s, c.alpha, c.beta, c.form == CLRSDP_GEMM_MIXED ? nullptr : ds, c.dmult);
+  StreamOwner so;
+  g.launch(so.s, c.alpha, c.beta, c.form == CLRSDP_GEMM_MIXED ? nullptr : ds, c.dmult);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(so.s));
   download_planes<T>(C, c.C, c.nc);
   return g.path();
 }
@@ -4422,11 +4344,9 @@ int chain_run(int device, const ChainCall& c) {
       ch.u.dot_part = dotp = up(c.dot_part, ndot);
     }
   }
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
-  ch.launch(s, c.a1, c.b1);
-  HIPCHK(hipStreamSynchronize(s));
+  StreamOwner so;
+  ch.launch(so.s, c.a1, c.b1);
+  HIPCHK(hipStreamSynchronize(so.s));
   if (trace) download_planes<double>(rout, c.rout, nx);
   for (int hf = 0; hf < (trace ? 0 : c.halves); ++hf) download_planes<double>(O[hf], c.O + hf * nn, nn);
   if (dotp) download_planes<double>(dotp, c.dot_part, ndot);
@@ -4480,9 +4400,8 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
   s1.finalize(); s2.finalize();
   PlanBase bd_owner;
   BlkDesc* d_big = big.empty() ? nullptr : bd_owner.own(big);
-  hipStream_t s = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+  StreamOwner so;
+  const hipStream_t s = so.s;
   ci.launch(s, info);
   g1.launch(s, 1.0, 0.0);
   g2.launch(s, 1.0, 0.0);
@@ -4521,11 +4440,6 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
 }
 
 // ---- clrsdp_reduce / clrsdp_slab_sum / clrsdp_update_state: the launch helpers above on planes
-struct StreamOwner {
-  hipStream_t s = nullptr;
-  StreamOwner() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~StreamOwner() { (void)hipStreamDestroy(s); }
-};
 template <class T>
 T from_limbs(const double* l) {
   T v = T(l[0]);
@@ -4968,22 +4882,26 @@ int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel) {
   return CLRSDP_OK;
 }
 
+// fn<word type>(...) for `words` (checked by the caller: 1, 2 or 4), errors into the return code
+#define WORDS_CALL(fn, ...)                                   \
+  try {                                                       \
+    if (words == 1) fn<double>(__VA_ARGS__);                  \
+    else if (words == 2) fn<mw::dd>(__VA_ARGS__);             \
+    else fn<mw::qd>(__VA_ARGS__);                             \
+    return CLRSDP_OK;                                         \
+  } catch (const ClrsdpError& e) {                            \
+    g_last_error = e.msg;                                     \
+    return e.code;                                            \
+  } catch (const std::exception& e) {                         \
+    g_last_error = e.what();                                  \
+    return CLRSDP_E_HIP;                                      \
+  }
+
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                       const double* A, double* min_eig) {
   if (nblocks <= 0 || !n || !A || !min_eig) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
-  try {
-    if (words == 1) eigmin_words<double>(device, nblocks, n, A, min_eig);
-    else if (words == 2) eigmin_words<mw::dd>(device, nblocks, n, A, min_eig);
-    else if (words == 4) eigmin_words<mw::qd>(device, nblocks, n, A, min_eig);
-    else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
-    return CLRSDP_OK;
-  } catch (const ClrsdpError& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return CLRSDP_E_HIP;
-  }
+  if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  WORDS_CALL(eigmin_words, device, nblocks, n, A, min_eig)
 }
 
 int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n, double* A,
@@ -4992,18 +4910,7 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
   if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
   for (int64_t b = 0; b < nblocks; ++b)
     if (n[b] <= 0 || n[b] > 4096) { g_last_error = "block size out of range"; return CLRSDP_E_ARG; }
-  try {
-    if (words == 1) getrf_words<double>(device, nblocks, n, A, perm, info);
-    else if (words == 2) getrf_words<mw::dd>(device, nblocks, n, A, perm, info);
-    else getrf_words<mw::qd>(device, nblocks, n, A, perm, info);
-    return CLRSDP_OK;
-  } catch (const ClrsdpError& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return CLRSDP_E_HIP;
-  }
+  WORDS_CALL(getrf_words, device, nblocks, n, A, perm, info)
 }
 
 int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nblocks,
@@ -5020,18 +4927,7 @@ int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nbl
       return CLRSDP_E_ARG;
     }
   }
-  try {
-    if (words == 1) potrf_words<double>(device, inverse, nblocks, n, A, info);
-    else if (words == 2) potrf_words<mw::dd>(device, inverse, nblocks, n, A, info);
-    else potrf_words<mw::qd>(device, inverse, nblocks, n, A, info);
-    return CLRSDP_OK;
-  } catch (const ClrsdpError& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return CLRSDP_E_HIP;
-  }
+  WORDS_CALL(potrf_words, device, inverse, nblocks, n, A, info)
 }
 
 int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans, int64_t nblocks,
@@ -5043,18 +4939,7 @@ int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans, 
     if (n[b] <= 0 || n[b] > 4096) { g_last_error = "block size out of range"; return CLRSDP_E_ARG; }
     if (nrhs[b] <= 0 || nrhs[b] > 4096) { g_last_error = "number of right-hand sides out of range"; return CLRSDP_E_ARG; }
   }
-  try {
-    if (words == 1) trsm_words<double>(device, mode, trans, nblocks, n, nrhs, A, B);
-    else if (words == 2) trsm_words<mw::dd>(device, mode, trans, nblocks, n, nrhs, A, B);
-    else trsm_words<mw::qd>(device, mode, trans, nblocks, n, nrhs, A, B);
-    return CLRSDP_OK;
-  } catch (const ClrsdpError& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return CLRSDP_E_HIP;
-  }
+  WORDS_CALL(trsm_words, device, mode, trans, nblocks, n, nrhs, A, B)
 }
 
 int32_t clrsdp_gemm(int32_t device, int32_t words, int32_t form, int32_t transa, int32_t transb,
@@ -5114,20 +4999,6 @@ int32_t clrsdp_gemm_chain(int32_t device, int32_t form, int64_t n, int64_t nprob
     return CLRSDP_E_HIP;
   }
 }
-
-#define WORDS_CALL(fn, ...)                                   \
-  try {                                                       \
-    if (words == 1) fn<double>(__VA_ARGS__);                  \
-    else if (words == 2) fn<mw::dd>(__VA_ARGS__);             \
-    else fn<mw::qd>(__VA_ARGS__);                             \
-    return CLRSDP_OK;                                         \
-  } catch (const ClrsdpError& e) {                            \
-    g_last_error = e.msg;                                     \
-    return e.code;                                            \
-  } catch (const std::exception& e) {                         \
-    g_last_error = e.what();                                  \
-    return CLRSDP_E_HIP;                                      \
-  }
 
 int32_t clrsdp_reduce(int32_t device, int32_t words, int32_t kind, int32_t op, int64_t n,
                       int64_t stride, const double* a, const double* b, const double* da,
