@@ -41,7 +41,7 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
            "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
            "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info",
-           "clrsdp_eigmin_kernel"]
+           "clrsdp_eigmin_kernel", "clrsdp_handoff_state"]
 # clrsdp_eigmin_kernel codes (include/clrsdp.h)
 EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK = range(6)
 EIG_K_NAMES = {0: "eigmin_split", 1: "eigmin_mx", 2: "eigmin_lds2", 3: "eigmin_lds",
@@ -160,6 +160,7 @@ def lib():
     L.clrsdp_comm_init.argtypes = [C.c_void_p, C.c_char_p]
     L.clrsdp_save_state.argtypes = [C.c_void_p]
     L.clrsdp_restore_state.argtypes = [C.c_void_p]
+    L.clrsdp_handoff_state.argtypes = [C.c_void_p, C.c_void_p]
     L.clrsdp_set_factorization.argtypes = [C.c_void_p, C.c_int32]
     L.clrsdp_get_factorization.argtypes = [C.c_void_p, P_i32]
     L.clrsdp_set_graph.argtypes = [C.c_void_p, C.c_int32]

@@ -1311,9 +1311,42 @@ void launch_update_state(hipStream_t s, T* X, const T* dX, T* Y, const T* dY, lo
                                         alpha_d, info, ninfo, part, sa);
 }
 
+// What clrsdp_handoff_state needs of a handle, whatever its word type: the four state arrays
+// (arrays of limb structs, `words` doubles per element), their counts, and a signature of the
+// description, rank, world size and owned set (equal signatures: equal local layouts).
+struct StateView {
+  void *x = nullptr, *X = nullptr, *Y = nullptr, *y = nullptr;
+  int64_t nx = 0, nblk_el = 0, n_y = 0;
+  int words = 0, dev = 0, inflight = 0;
+  bool has_state = false;
+  hipStream_t stream = nullptr;
+  std::vector<int64_t> sig;
+};
+
+template <class TS, class TD>
+void launch_state_convert(hipStream_t s, const StateView& src, const StateView& dst) {
+  const long long tot = (long long)src.nx + 2 * (long long)src.nblk_el + (long long)src.n_y;
+  if (tot <= 0) return;
+  const StateSegs<const TS> a{static_cast<const TS*>(src.x), static_cast<const TS*>(src.X),
+                              static_cast<const TS*>(src.Y), static_cast<const TS*>(src.y),
+                              src.nx, src.nblk_el, src.n_y};
+  const StateSegs<TD> b{static_cast<TD*>(dst.x), static_cast<TD*>(dst.X), static_cast<TD*>(dst.Y),
+                        static_cast<TD*>(dst.y), dst.nx, dst.nblk_el, dst.n_y};
+  state_convert<TS, TD><<<(unsigned)std::min<long long>((tot + 255) / 256, 2048), 256, 0, s>>>(a, b);
+}
+// the nine (source, destination) word pairs, by the index of the width (1, 2, 4 words)
+using StateConvertFn = void (*)(hipStream_t, const StateView&, const StateView&);
+inline int width_index(int words) { return words == 1 ? 0 : words == 2 ? 1 : words == 4 ? 2 : -1; }
+static const StateConvertFn state_convert_fn[3][3] = {
+    {launch_state_convert<double, double>, launch_state_convert<double, dd>, launch_state_convert<double, qd>},
+    {launch_state_convert<dd, double>, launch_state_convert<dd, dd>, launch_state_convert<dd, qd>},
+    {launch_state_convert<qd, double>, launch_state_convert<qd, dd>, launch_state_convert<qd, qd>}};
+
 struct HandleBase {
   std::string err;
   int dev = 0;  // the handle's HIP device (every C-ABI call on the handle runs with it current)
+  virtual StateView state_view() const = 0;
+  virtual void adopt_state() = 0;  // the bookkeeping of set_state after the state was written on the device
   virtual ~HandleBase() {}
   virtual void upload(const double* V, const double* lam, const double* B, const double* c,
                       const double* b, const double* C) = 0;
@@ -2604,15 +2637,36 @@ struct Solver final : HandleBase {
   }
 
   void set_state(const double* xh, const double* Xh, const double* yh, const double* Yh) override {
-    body.dy_dot_ready = false;  // (a new state: CORRECTOR_R sums <X + dX, Y + dY> itself)
     for (int c = 0; c < nc(); ++c) put(x + c_xoff[c], xh, tot_x, xoff_g[oc[c]], Ds[oc[c]]);
     for (const LBlk& b : lb) {
       put(X + b.off, Xh, tot_blk, blkoff_g[b.gjl], (int64_t)b.n * b.n);
       put(Y + b.off, Yh, tot_blk, blkoff_g[b.gjl], (int64_t)b.n * b.n);
     }
     put(y, yh, n_y, 0, n_y);
+    adopt_state();
+  }
+  bool has_state = false;  // set_state or a hand-off has given the handle an iterate
+  // after the state was written (set_state's uploads, clrsdp_handoff_state's launch)
+  void adopt_state() override {
+    body.dy_dot_ready = false;  // (a new state: CORRECTOR_R sums <X + dX, Y + dY> itself)
+    has_state = true;
     refresh_xy_part();
     HIPCHK(hipStreamSynchronize(stream));
+  }
+  StateView state_view() const override {
+    StateView v;
+    v.x = x; v.X = X; v.Y = Y; v.y = y;
+    v.nx = nx; v.nblk_el = nblk_el; v.n_y = n_y;
+    v.words = Num<T>::W; v.dev = device; v.inflight = inflight; v.has_state = has_state;
+    v.stream = stream;
+    // every vector behind its length, so that two signatures agree only part by part
+    auto add = [&](const auto& a) {
+      v.sig.push_back((int64_t)a.size());
+      for (const auto& e : a) v.sig.push_back((int64_t)e);
+    };
+    v.sig = {J, n_y, (int64_t)rank, (int64_t)world};
+    add(m); add(Lc); add(Ns); add(delta); add(ranks_all); add(oc);
+    return v;
   }
   void get_state(double* xh, double* Xh, double* yh, double* Yh) override {
     if (xh)
@@ -4719,6 +4773,28 @@ static int guard_dev(const clrsdp_handle* h) {
   return d;
 }
 
+// clrsdp_handoff_state: refusals first (nothing is touched before the last of them)
+static void handoff_state(clrsdp_handle* dst, clrsdp_handle* src) {
+  if (dst == src) throw ClrsdpError{CLRSDP_E_ARG, "handoff_state: source and destination are the same handle"};
+  const StateView s = src->impl->state_view();
+  const StateView d = dst->impl->state_view();
+  if (s.dev != d.dev) throw ClrsdpError{CLRSDP_E_ARG, "handoff_state: the handles are on different devices"};
+  if (s.sig != d.sig || s.nx != d.nx || s.nblk_el != d.nblk_el || s.n_y != d.n_y)
+    throw ClrsdpError{CLRSDP_E_ARG, "handoff_state: the handles differ in their description, rank, "
+                                    "world size or owned clusters"};
+  if (s.inflight || d.inflight) throw ClrsdpError{CLRSDP_E_STATE, "handoff_state with loop bodies in flight"};
+  if (!s.has_state) throw ClrsdpError{CLRSDP_E_STATE, "handoff_state: the source handle has no state yet"};
+  const int si = width_index(s.words);
+  const int di = width_index(d.words);
+  if (si < 0 || di < 0) throw ClrsdpError{CLRSDP_E_ARG, "handoff_state: unknown word width"};
+  // after the source's stream work, on the destination's stream; adopt_state waits for it, so
+  // the source may be destroyed once this returns
+  HIPCHK(hipStreamSynchronize(s.stream));
+  state_convert_fn[si][di](d.stream, s, d);
+  HIPCHK(hipGetLastError());
+  dst->impl->adopt_state();
+}
+
 extern "C" {
 
 int32_t clrsdp_version(void) { return 100; }
@@ -4853,6 +4929,11 @@ int32_t clrsdp_save_state(clrsdp_handle* h) {
 int32_t clrsdp_restore_state(clrsdp_handle* h) {
   if (!h) { g_last_error = "null handle"; return CLRSDP_E_ARG; }
   GUARD(h, { h->impl->restore_state(); return CLRSDP_OK; })
+}
+
+int32_t clrsdp_handoff_state(clrsdp_handle* dst, clrsdp_handle* src) {
+  if (!dst || !src) { g_last_error = "null handle"; return CLRSDP_E_ARG; }
+  GUARD(dst, { handoff_state(dst, src); return CLRSDP_OK; })
 }
 
 int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, const double* M,

@@ -3280,6 +3280,38 @@ __global__ void copy_guard2(void* __restrict__ d0, const void* __restrict__ s0, 
   if (d1) seg(d1, s1, b1);
 }
 
+// The iterate of one handle into another of the same description and owned set at another word
+// width (clrsdp_handoff_state): element-wise over the four segments x, X, Y, y, whose local
+// layouts agree.  Limbs are moved as doubles, no arithmetic: wider = the source limbs then exact
+// zeros, equal = a bitwise copy, narrower = the leading limbs (the words are renormalised, so
+// that is the value at the narrower width).
+template <class T>
+struct StateSegs {
+  T *x, *X, *Y, *y;
+  long long nx, nblk, ny;
+};
+template <class TS, class TD>
+__global__ __launch_bounds__(256) void state_convert(StateSegs<const TS> s, StateSegs<TD> d) {
+  constexpr int WS = Num<TS>::W, WD = Num<TD>::W, WC = WS < WD ? WS : WD;
+  static_assert(sizeof(TS) == WS * sizeof(double) && sizeof(TD) == WD * sizeof(double), "limb structs");
+  const long long e1 = s.nx, e2 = e1 + s.nblk, e3 = e2 + s.nblk, tot = e3 + s.ny;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < tot;
+       e += (long long)gridDim.x * blockDim.x) {
+    const TS* sp;
+    TD* dp;
+    if (e < e1) { sp = s.x + e; dp = d.x + e; }
+    else if (e < e2) { sp = s.X + (e - e1); dp = d.X + (e - e1); }
+    else if (e < e3) { sp = s.Y + (e - e2); dp = d.Y + (e - e2); }
+    else { sp = s.y + (e - e3); dp = d.y + (e - e3); }
+    const double* sl = reinterpret_cast<const double*>(sp);
+    double* dl = reinterpret_cast<double*>(dp);
+#pragma unroll
+    for (int q = 0; q < WC; ++q) dl[q] = sl[q];
+#pragma unroll
+    for (int q = WC; q < WD; ++q) dl[q] = 0.0;
+  }
+}
+
 template <class T>
 __global__ void vec_fill(T* out, double v, long long n) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
 import numpy as np
@@ -235,6 +235,13 @@ class DeviceSolver:
     def restore_state(self):
         """Restore the last snapshot, stream-ordered after the work already enqueued."""
         self.check(self.L.clrsdp_restore_state(self.h))
+
+    def handoff_state_to(self, other: "DeviceSolver"):
+        """clrsdp_handoff_state: copy x, X, y, Y into ``other`` on the device; ``other`` may have
+        another precision_words (wider: the limbs then zeros; narrower: the leading limbs) but
+        needs the same description, device and owned clusters.  ``other`` is then as after
+        ``set_state`` (call ``initial_residuals`` next) and this handle may be closed."""
+        _lib.check(self.L.clrsdp_handoff_state(other.h, self.h), other.h)
 
     def set_factorization(self, flags: int):
         """clrsdp_set_factorization: FACT_FALLBACK (default: pivoted LU once a Cholesky fails),
@@ -938,6 +945,9 @@ class RunInfo:
     factorization: int = 1  # clrsdp_get_factorization at the end (an LU fallback adds its flag)
     lu_switch: int = 0      # iteration whose loop body switched to LU (0: none)
     inner_ms: np.ndarray = None  # the reference's inner buckets summed from iteration 3 (ms)
+    # solve_escalating: per width (words, first iteration, bodies, reason), reason one of floor,
+    # stalled, failed:<code>, terminated, maxiterations (empty for solverank1sdp)
+    stages: list = field(default_factory=list)
 
 
 def _stage_groups(ph):
@@ -984,6 +994,192 @@ def _time_spent(total, ph, inner=None):
     return "\n".join(lines) + "\n"
 
 
+# a loop body that failed this way applied no update (the device guards the state update by the
+# status words), so the state before it can be handed to a wider handle (solve_escalating)
+STAGE_FAIL_CODES = (_lib.E_NOT_PD_X, _lib.E_NOT_PD_S, _lib.E_NOT_PD_Q, _lib.E_STEP)
+
+
+class _Loop:
+    """The loop control of ``solverank1sdp`` (MPMP.jl:720-1025 around the loop body): the values
+    terminate() looks at, the log, the timers and the returned tuple.  ``solverank1sdp`` drives
+    one handle with it, ``solve_escalating`` one handle per width, one after the other."""
+
+    def __init__(self, prm_v, b0, need_primal_feasible, need_dual_feasible, out, testing,
+                 record_exact):
+        self.prm_v, self.b0, self.b0f = prm_v, b0, float(b0)
+        self.need_p, self.need_d = need_primal_feasible, need_dual_feasible
+        self.out, self.testing, self.record_exact = out, testing, record_exact
+        self.it = 1
+        self.log = []
+        self.phase = np.zeros(_lib.NUM_STAGES)
+        self.inner = np.zeros(_lib.NUM_INNER)
+        self.t_start = None
+        self.t_after2 = None
+        self.status = "maxiterations"
+        self.exact = []
+        self.lu_switch = 0
+        self.history = []   # the gap of every state a body of the current handle produced
+
+    def attach(self, dev):
+        """Loop control at the state's full width (MPMP.jl:942-945, 1067-1078, 1147-1185 run at
+        the working precision): at dd/qd the thresholds are the device's exact multi-word values
+        and the gap, errors and pd_feas are the device's own control_update results (all limbs),
+        so a threshold below fp64 resolution is decided at the word's precision, and the
+        synchronous and pipelined loops decide alike."""
+        self.dev = dev
+        self.exact_ctl = dev.w > 1
+        self.gthr = device_threshold(self.prm_v["duality_gap_threshold"], dev.w)
+        self.pthr = device_threshold(self.prm_v["primal_error_threshold"], dev.w)
+        self.dthr = device_threshold(self.prm_v["dual_error_threshold"], dev.w)
+        self.fact_seen = dev.factorization
+        self.timed = bool(getattr(dev, "timing", False))
+        self.history = []
+
+    def device_control(self, st):
+        """(gap, primal error, dual error) of the device's control_update for the state after
+        the body `st` reports, all limbs (exact mpmath sums)."""
+        import mpmath
+        w = self.dev.w
+
+        def v(limbs_):
+            r = mpmath.mpf(0)
+            for x in list(limbs_)[:w]:
+                r = mpmath.fadd(r, x, exact=True)
+            return r
+        return v(st.gap_w), max(v(st.P_err_w), v(st.p_err_w)), v(st.d_err_w)
+
+    def start(self, st, handed_over=False):
+        """From the stats of initial_residuals.  The gap of the initial point excludes b0
+        (compute_duality_gap(constraints, x, y, Y, C, b), MPMP.jl:725, 1067-1074); a state handed
+        over from a narrower handle is an iterate of the running loop, whose gap includes it
+        (MPMP.jl:942)."""
+        b0f = self.b0f
+        self.p_obj, self.d_obj = p_obj, d_obj = st.p_obj, st.d_obj
+        if handed_over:
+            self.dual_gap = abs(p_obj - d_obj) / max(1.0, abs(p_obj + d_obj))
+        else:
+            self.dual_gap = abs((p_obj - b0f) - (d_obj - b0f)) / max(1.0, abs((p_obj - b0f) + (d_obj - b0f)))
+        self.perr = max(st.p_err, st.P_err)
+        self.derr = st.d_err
+        if self.exact_ctl:
+            self.dual_gap, self.perr, self.derr = self.device_control(st)
+            if handed_over:
+                import mpmath
+                with mpmath.workprec(64 * self.dev.w + 64):
+                    sc = self.dev.buffer(_lib.BUF_SCALARS, exact=True)
+                    pp, dd_ = +sc[_lib.SC["p_obj"]], +sc[_lib.SC["d_obj"]]
+                    self.dual_gap = abs(pp - dd_) / max(mpmath.mpf(1), abs(pp + dd_))
+        self.pd_feas = self.perr < self.pthr and self.derr < self.dthr
+        if self.t_start is None:
+            self.t_start = time.time()
+
+    def record(self, st):
+        dev, out = self.dev, self.out
+        f = dev.factorization
+        if f != self.fact_seen:   # the device switched to LU for the rest of the solve
+            if (f & ~self.fact_seen) & _lib.FACT_LU_X:
+                out("The inverse of X could not be computed with the cholesky factorization. We "
+                    "switch to using the LU decomposition.")
+            if (f & ~self.fact_seen) & _lib.FACT_LU_SQ:
+                out("The Cholesky factorization of S or Q failed. We switch to the pivoted LU "
+                    "decomposition (approx_lu!) for S and Q.")
+            self.fact_seen = f
+            self.lu_switch = self.lu_switch or self.it
+        if self.it > 2:
+            self.phase[:] += np.array(st.phase_ms[:])
+            self.inner[:] += np.array(st.inner_ms[:])
+        elif self.testing and self.timed:  # MPMP.jl:899-920: the times of the first iterations
+            out(_first_iteration_times(np.array(st.phase_ms[:]) / 1e3))
+        row = log_row(self.it, time.time() - self.t_start, st, self.p_obj, self.d_obj, self.dual_gap)
+        self.log.append(row)
+        out("%5d %8.1f %11.3e %11.3e %11.3e %10.2e %10.2e %10.2e %10.2e %10.2e %10.2e %10.2e" % row)
+        self.p_obj, self.d_obj = st.p_obj, st.d_obj
+        if self.exact_ctl:   # the device's full-width values (dd/qd)
+            self.dual_gap, self.perr, self.derr = self.device_control(st)
+        else:
+            self.dual_gap = abs(self.p_obj - self.d_obj) / max(1.0, abs(self.p_obj + self.d_obj))  # MPMP.jl:942
+            self.perr = max(st.p_err, st.P_err)                                # MPMP.jl:943
+            self.derr = st.d_err
+        self.it += 1
+        self.pd_feas = self.perr < self.pthr and self.derr < self.dthr         # MPMP.jl:949-953
+        self.history.append(self.dual_gap)
+
+    def term(self):
+        return _terminate(self.dual_gap, self.perr, self.derr, self.gthr, self.pthr, self.dthr,
+                          self.need_p, self.need_d, self.out)
+
+    def run_sync(self, prm, maxiterations, stop=None, fail_codes=()):
+        """The synchronous loop on the attached handle: one ``clrsdp_iterate`` per body, the host
+        decides pd_feas and terminate().  Returns why it ended: "terminated", "maxiterations",
+        what ``stop(history)`` answered (asked after terminate() and the iteration bound, on the
+        gaps of the states this handle's bodies produced), or "failed:<code>" when a body raised a
+        ClrsdpError whose code is in ``fail_codes`` (the state is then the one before that body)."""
+        dev = self.dev
+        while True:
+            if self.term():
+                self.status = "terminated"
+                return "terminated"
+            if not self.it < maxiterations:
+                return "maxiterations"
+            why = stop(self.history) if stop is not None else None
+            if why:
+                return why
+            if self.it == 3:
+                self.t_after2 = time.time()
+            try:
+                st = dev.iterate(prm, self.pd_feas)
+            except _lib.ClrsdpError as e:
+                if e.code in fail_codes:
+                    return "failed:%d" % e.code
+                raise
+            if self.record_exact:
+                sc = dev.buffer(_lib.BUF_SCALARS, exact=True)
+                self.exact.append({k: sc[v] for k, v in _lib.SC.items()})
+            self.record(st)
+
+    def result(self, return_info, stages=None):
+        """The table's footer and the returned tuple (MPMP.jl:973-1024) from the attached handle."""
+        dev, out, b0f = self.dev, self.out, self.b0f
+        p_obj, d_obj = self.p_obj, self.d_obj
+        t_total = time.time() - self.t_start
+        out(HEADER)
+        out(_time_spent(t_total, self.phase / 1e3 if self.timed else None,
+                        self.inner / 1e3 if self.timed else None))
+        xf, Xf, yf, Yf = dev.get_state()
+        P, d = dev.global_P_d()
+        p = dev.buffer(_lib.BUF_PVEC)
+        gap_nob0 = abs((p_obj - b0f) - (d_obj - b0f)) / max(1.0, abs((p_obj - b0f) + (d_obj - b0f)))
+        ret_p, ret_d = p_obj, d_obj
+        if dev.w > 1:
+            # MPMP.jl:1021-1023 at the state's precision: the device's objectives of the final state
+            # (all limbs) and the gap without b0 from them
+            import mpmath
+            with mpmath.workprec(64 * dev.w + 64):
+                sc = dev.buffer(_lib.BUF_SCALARS, exact=True)
+                ret_p, ret_d = +sc[_lib.SC["p_obj"]], +sc[_lib.SC["d_obj"]]
+                b0m = mpmath.mpf(self.b0)
+                pp, dd_ = ret_p - b0m, ret_d - b0m
+                gap_nob0 = abs(pp - dd_) / max(mpmath.mpf(1), abs(pp + dd_))
+        res = (xf, Xf, yf, Yf, P, p, d, gap_nob0, ret_p, ret_d, t_total)
+        if return_info:
+            info = RunInfo(self.it - 1, self.log, self.phase, t_total,
+                           (time.time() - self.t_after2) if self.t_after2 else 0.0, self.status,
+                           self.exact, dev.factorization, self.lu_switch, self.inner)
+            if stages is not None:
+                info.stages = list(stages)
+            res = res + (info,)
+        return res
+
+
+def _solver_params(beta_infeasible, beta_feasible, gamma, omega_p, omega_d, duality_gap_threshold,
+                   primal_error_threshold, dual_error_threshold):
+    kw = dict(beta_infeasible=beta_infeasible, beta_feasible=beta_feasible, gamma=gamma,
+              omega_p=omega_p, omega_d=omega_d, duality_gap_threshold=duality_gap_threshold,
+              primal_error_threshold=primal_error_threshold,
+              dual_error_threshold=dual_error_threshold)
+    return {k: (DEFAULTS[k] if v is None else v) for k, v in kw.items()}
+
+
 def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterations=500,
                   beta_infeasible=None, beta_feasible=None, gamma=None, omega_p=None,
                   omega_d=None, duality_gap_threshold=None, primal_error_threshold=None,
@@ -1008,25 +1204,14 @@ def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterati
     log rows (RunInfo.log) are floats except the gap column, which is an mpmath number at dd/qd
     like the returned gap (:func:`log_row`).
     """
-    kw = dict(beta_infeasible=beta_infeasible, beta_feasible=beta_feasible, gamma=gamma,
-              omega_p=omega_p, omega_d=omega_d, duality_gap_threshold=duality_gap_threshold,
-              primal_error_threshold=primal_error_threshold,
-              dual_error_threshold=dual_error_threshold)
-    prm_v = {k: (DEFAULTS[k] if v is None else v) for k, v in kw.items()}
+    prm_v = _solver_params(beta_infeasible, beta_feasible, gamma, omega_p, omega_d,
+                           duality_gap_threshold, primal_error_threshold, dual_error_threshold)
     out = print if verbose else (lambda *a, **k: None)
     bi = blockinfo
     dev = solver or DeviceSolver(constraints, b, bi, precision_words=precision_words, C_blocks=C,
                                  device=device)
     prm = make_params(prm_v["beta_infeasible"], prm_v["beta_feasible"], prm_v["gamma"], b0)
-    # loop control at the state's full width (MPMP.jl:942-945, 1067-1078, 1147-1185 run at the
-    # working precision): at dd/qd the thresholds are the device's exact multi-word values and
-    # the gap, errors and pd_feas are the device's own control_update results (all limbs), so a
-    # threshold below fp64 resolution is decided at the word's precision, and the synchronous
-    # and pipelined loops decide alike
-    exact_ctl = dev.w > 1
-    gthr = device_threshold(prm_v["duality_gap_threshold"], dev.w)
-    pthr = device_threshold(prm_v["primal_error_threshold"], dev.w)
-    dthr = device_threshold(prm_v["dual_error_threshold"], dev.w)
+    loop = _Loop(prm_v, b0, need_primal_feasible, need_dual_feasible, out, testing, record_exact)
     if initial_solutions is not None and len(initial_solutions) == 4:
         x, X, y, Y = initial_solutions
     else:
@@ -1034,8 +1219,7 @@ def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterati
     dev.set_state(x, X, y, Y)
     if factorization is not None:
         dev.set_factorization(factorization)
-    fact_seen = dev.factorization
-    b0f = float(b0)
+    loop.attach(dev)
     if pipelined is None:
         # one GPU: the hipGraph replay leaves only a short host round trip between bodies and
         # the synchronous loop measured faster; sharded: enqueueing (exchange callbacks, no
@@ -1045,73 +1229,7 @@ def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterati
                                  prm_v["dual_error_threshold"], need_primal_feasible,
                                  need_dual_feasible))
     out(HEADER)
-    st = dev.initial_residuals(prm)
-    p_obj, d_obj = st.p_obj, st.d_obj
-    # compute_duality_gap(constraints, x, y, Y, C, b) excludes b0 (MPMP.jl:725, 1067-1074)
-    dual_gap = abs((p_obj - b0f) - (d_obj - b0f)) / max(1.0, abs((p_obj - b0f) + (d_obj - b0f)))
-    perr = max(st.p_err, st.P_err)
-    derr = st.d_err
-
-    def device_control(st):
-        """(gap, primal error, dual error) of the device's control_update for the state after
-        the body `st` reports, all limbs (exact mpmath sums)."""
-        import mpmath
-
-        def v(limbs_):
-            r = mpmath.mpf(0)
-            for x in list(limbs_)[:dev.w]:
-                r = mpmath.fadd(r, x, exact=True)
-            return r
-        return v(st.gap_w), max(v(st.P_err_w), v(st.p_err_w)), v(st.d_err_w)
-
-    if exact_ctl:
-        dual_gap, perr, derr = device_control(st)
-    pd_feas = perr < pthr and derr < dthr
-    it = 1
-    log = []
-    phase = np.zeros(_lib.NUM_STAGES)
-    inner = np.zeros(_lib.NUM_INNER)
-    t_start = time.time()
-    t_after2 = None
-    status = "maxiterations"
-    exact = []
-    lu_switch = [0]
-
-    timed = bool(getattr(dev, "timing", False))
-
-    def record(st):
-        nonlocal p_obj, d_obj, dual_gap, perr, derr, pd_feas, it, fact_seen
-        f = dev.factorization
-        if f != fact_seen:   # the device switched to LU for the rest of the solve
-            if (f & ~fact_seen) & _lib.FACT_LU_X:
-                out("The inverse of X could not be computed with the cholesky factorization. We "
-                    "switch to using the LU decomposition.")
-            if (f & ~fact_seen) & _lib.FACT_LU_SQ:
-                out("The Cholesky factorization of S or Q failed. We switch to the pivoted LU "
-                    "decomposition (approx_lu!) for S and Q.")
-            fact_seen = f
-            lu_switch[0] = lu_switch[0] or it
-        if it > 2:
-            phase[:] += np.array(st.phase_ms[:])
-            inner[:] += np.array(st.inner_ms[:])
-        elif testing and timed:  # MPMP.jl:899-920: the times of the first iterations
-            out(_first_iteration_times(np.array(st.phase_ms[:]) / 1e3))
-        row = log_row(it, time.time() - t_start, st, p_obj, d_obj, dual_gap)
-        log.append(row)
-        out("%5d %8.1f %11.3e %11.3e %11.3e %10.2e %10.2e %10.2e %10.2e %10.2e %10.2e %10.2e" % row)
-        p_obj, d_obj = st.p_obj, st.d_obj
-        if exact_ctl:   # the device's full-width values (dd/qd)
-            dual_gap, perr, derr = device_control(st)
-        else:
-            dual_gap = abs(p_obj - d_obj) / max(1.0, abs(p_obj + d_obj))      # MPMP.jl:942
-            perr = max(st.p_err, st.P_err)                                     # MPMP.jl:943
-            derr = st.d_err
-        it += 1
-        pd_feas = perr < pthr and derr < dthr                                  # MPMP.jl:949-953
-
-    def term():
-        return _terminate(dual_gap, perr, derr, gthr, pthr, dthr, need_primal_feasible,
-                          need_dual_feasible, out)
+    loop.start(dev.initial_residuals(prm))
 
     if pipelined:
         # the host one loop body behind: body it+1 is enqueued before the log row of body it is
@@ -1119,24 +1237,24 @@ def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterati
         # enqueued after termination applies nothing (ran = False)
         inflight = 0
         halted = False
-        if term():
-            status = "terminated"
-        elif it < maxiterations:
+        if loop.term():
+            loop.status = "terminated"
+        elif loop.it < maxiterations:
             dev.iterate_async(prm)
             inflight = 1
         try:
             while inflight:
-                if it + 1 < maxiterations:
+                if loop.it + 1 < maxiterations:
                     dev.iterate_async(prm)
                     inflight += 1
-                if it == 3:
-                    t_after2 = time.time()
+                if loop.it == 3:
+                    loop.t_after2 = time.time()
                 st, ran = dev.iterate_wait()
                 inflight -= 1
                 if not ran:
                     halted = True
                     break
-                record(st)
+                loop.record(st)
         finally:
             while inflight:   # drain skipped bodies (or the one behind a failure)
                 try:
@@ -1144,46 +1262,149 @@ def solverank1sdp(constraints, b, blockinfo: BlockInfo, C=None, b0=0, maxiterati
                 except Exception:
                     pass
                 inflight -= 1
-        if it > 1 or halted:
+        if loop.it > 1 or halted:
             # the reference evaluates terminate() (which prints the reason) before iter < maxit
-            if term() or halted:
-                status = "terminated"
-    while not pipelined:
-        if term():
-            status = "terminated"
-            break
-        if not it < maxiterations:
-            break
-        if it == 3:
-            t_after2 = time.time()
-        st = dev.iterate(prm, pd_feas)
-        if record_exact:
-            sc = dev.buffer(_lib.BUF_SCALARS, exact=True)
-            exact.append({k: sc[v] for k, v in _lib.SC.items()})
-        record(st)
-    t_total = time.time() - t_start
-    out(HEADER)
-    out(_time_spent(t_total, phase / 1e3 if timed else None, inner / 1e3 if timed else None))
-    xf, Xf, yf, Yf = dev.get_state()
-    P, d = dev.global_P_d()
-    p = dev.buffer(_lib.BUF_PVEC)
-    gap_nob0 = abs((p_obj - b0f) - (d_obj - b0f)) / max(1.0, abs((p_obj - b0f) + (d_obj - b0f)))
-    ret_p, ret_d = p_obj, d_obj
-    if dev.w > 1:
-        # MPMP.jl:1021-1023 at the state's precision: the device's objectives of the final state
-        # (all limbs) and the gap without b0 from them
-        import mpmath
-        with mpmath.workprec(64 * dev.w + 64):
-            sc = dev.buffer(_lib.BUF_SCALARS, exact=True)
-            ret_p, ret_d = +sc[_lib.SC["p_obj"]], +sc[_lib.SC["d_obj"]]
-            b0m = mpmath.mpf(b0)
-            pp, dd_ = ret_p - b0m, ret_d - b0m
-            gap_nob0 = abs(pp - dd_) / max(mpmath.mpf(1), abs(pp + dd_))
-    res = (xf, Xf, yf, Yf, P, p, d, gap_nob0, ret_p, ret_d, t_total)
-    if return_info:
-        res = res + (RunInfo(it - 1, log, phase, t_total,
-                             (time.time() - t_after2) if t_after2 else 0.0, status, exact,
-                             dev.factorization, lu_switch[0], inner),)
+            if loop.term() or halted:
+                loop.status = "terminated"
+    else:
+        loop.run_sync(prm, maxiterations)
+    res = loop.result(return_info)
     if solver is None:
         dev.close()
     return res
+
+
+# the default hand-over floors of solve_escalating: the square root of the width's unit roundoff.
+# The Newton system's conditioning grows like 1/mu, so its rounding error u/mu passes mu there;
+# each sits two decades inside the recorded reach of its width (fp64: gap 1.3e-10 on the
+# polynomial-minimum instance; double-double: 1e-20 on the golden instances with a
+# stall near 1e-22)
+GAP_FLOORS = {1: 1e-8, 2: 1e-16}
+
+
+def stage_decision(history, floor, patience):
+    """Whether a non-final width of :func:`solve_escalating` hands its iterate over now; a pure
+    function of ``history``, the duality gaps of the states this width's loop bodies produced, in
+    order (the state the width started from is not among them).  Asked after terminate() at the
+    caller's thresholds.  Returns
+
+    * ``"floor"`` when the last two gaps are both below ``floor`` (0 or None: no floor).  Two in
+      a row, both produced by bodies of this width: the gap is 0 at the initial point and can
+      cross zero while the iterate is still infeasible;
+    * ``"stalled"`` when the last ``patience`` states set no new minimum of this width's gap (a
+      width that has reached its precision wanders; its step lengths do not show it);
+    * ``None`` otherwise."""
+    h = list(history)
+    if floor and len(h) >= 2 and h[-1] < floor and h[-2] < floor:
+        return "floor"
+    patience = int(patience)
+    if patience > 0 and len(h) > patience and not min(h[-patience:]) < min(h[:-patience]):
+        return "stalled"
+    return None
+
+
+def solve_escalating(constraints, b, blockinfo: BlockInfo, widths=(1, 2, 4), gap_floors=None,
+                     patience=5, C=None, b0=0, maxiterations=500, beta_infeasible=None,
+                     beta_feasible=None, gamma=None, omega_p=None, omega_d=None,
+                     duality_gap_threshold=None, primal_error_threshold=None,
+                     dual_error_threshold=None, need_primal_feasible=False,
+                     need_dual_feasible=False, testing=True, initial_solutions=(),
+                     precision_words=None, device=0, verbose=True, solver=None, return_info=False,
+                     record_exact=False, pipelined=None, factorization: Optional[int] = None,
+                     solver_factory=None):
+    """One solve across word widths: :func:`solverank1sdp`'s synchronous loop, run at
+    ``widths[0]`` while that is good enough and continued at the next width from the same iterate
+    (``DeviceSolver.handoff_state_to``, device to device), down to the last width, whose behaviour
+    is solverank1sdp's, errors included.  ``widths`` is strictly increasing, from {1, 2, 4}.
+
+    A non-final width ends (:func:`stage_decision`, after terminate() at the caller's thresholds,
+    which ends the solve at that width as today) when two states in a row have a gap below its
+    floor (``gap_floors``, one per non-final width, default :data:`GAP_FLOORS`; 0: no floor), when
+    ``patience`` states in a row set no new minimum of its gap, or when a loop body fails with
+    E_NOT_PD_X / _S / _Q or E_STEP after the handle's own LU fallback (the device applied no
+    update, so the state before that body is handed over).  An early hand-over costs only time
+    and a late one only loop bodies, so no result depends on these values.
+
+    One handle per width, created when its stage starts and closed after its hand-over; each
+    uploads the constraints at its own width and gets ``factorization`` afresh (an LU fallback of
+    the narrower width is not inherited).  ``maxiterations`` bounds the bodies of all widths
+    together; iteration numbers and the time column continue; a line announces each switch.
+    Returns the tuple of the width the solve ended at; ``RunInfo.stages`` lists
+    ``(words, first iteration, bodies, reason)`` with reason one of floor, stalled,
+    failed:<code>, terminated, maxiterations.
+
+    ``precision_words``, ``solver`` and ``pipelined=True`` contradict ``widths`` and raise
+    ValueError, as does a handle sharded over ranks: every rank would decide alike (the gap is
+    replicated and the status words are OR-ed over the ranks), but that has not been run.
+    ``solver_factory(words)`` replaces the DeviceSolver construction (tests)."""
+    widths = tuple(int(w) for w in widths)
+    if not widths or any(w not in (1, 2, 4) for w in widths) or \
+            any(a >= c for a, c in zip(widths, widths[1:])):
+        raise ValueError("widths: strictly increasing, from 1, 2, 4")
+    if precision_words is not None or solver is not None or pipelined:
+        raise ValueError("solve_escalating creates one synchronous handle per width: "
+                         "precision_words, solver and pipelined=True do not apply")
+    if gap_floors is None:
+        floors = [GAP_FLOORS[w] for w in widths[:-1]]
+    else:
+        floors = [float(f) for f in gap_floors]
+        if len(floors) != len(widths) - 1 or any(f < 0 for f in floors):
+            raise ValueError("gap_floors: one value >= 0 per non-final width")
+    prm_v = _solver_params(beta_infeasible, beta_feasible, gamma, omega_p, omega_d,
+                           duality_gap_threshold, primal_error_threshold, dual_error_threshold)
+    out = print if verbose else (lambda *a, **k: None)
+    bi = blockinfo
+    if solver_factory is None:
+        def solver_factory(words):
+            return DeviceSolver(constraints, b, bi, precision_words=words, C_blocks=C, device=device)
+    prm = make_params(prm_v["beta_infeasible"], prm_v["beta_feasible"], prm_v["gamma"], b0)
+    ctl = make_control(prm_v["duality_gap_threshold"], prm_v["primal_error_threshold"],
+                       prm_v["dual_error_threshold"], need_primal_feasible, need_dual_feasible)
+    loop = _Loop(prm_v, b0, need_primal_feasible, need_dual_feasible, out, testing, record_exact)
+    stages = []
+    prev = dev = None
+    reason = None
+    try:
+        for k, w in enumerate(widths):
+            dev = solver_factory(w)
+            if getattr(dev, "world", 1) > 1:
+                raise ValueError("solve_escalating does not run sharded over ranks")
+            if prev is None:
+                if initial_solutions is not None and len(initial_solutions) == 4:
+                    x, X, y, Y = initial_solutions
+                else:
+                    x, X, y, Y = initial_point(bi, float(prm_v["omega_p"]), float(prm_v["omega_d"]))
+                dev.set_state(x, X, y, Y)
+            else:
+                prev.handoff_state_to(dev)
+                prev.close()
+                prev = None
+                out("Continuing at %d words from %d at iteration %d (%s)" % (
+                    w, widths[k - 1], loop.it, reason))
+            if factorization is not None:
+                dev.set_factorization(factorization)
+            loop.attach(dev)
+            dev.set_control(ctl)
+            if k == 0:
+                out(HEADER)
+            loop.start(dev.initial_residuals(prm), handed_over=k > 0)
+            last = k == len(widths) - 1
+            first = loop.it
+            if last:
+                reason = loop.run_sync(prm, maxiterations)
+            else:
+                floor = floors[k]
+                reason = loop.run_sync(prm, maxiterations,
+                                       stop=lambda h: stage_decision(h, floor, patience),
+                                       fail_codes=STAGE_FAIL_CODES)
+            stages.append((w, first, loop.it - first, reason))
+            if reason in ("terminated", "maxiterations"):
+                break
+            prev, dev = dev, None
+        return loop.result(return_info, stages)
+    finally:
+        for h in (prev, dev):
+            if h is not None:
+                h.close()
+
+

@@ -268,6 +268,34 @@ int32_t clrsdp_comm_init(clrsdp_handle* h, const uint8_t* id);
 int32_t clrsdp_save_state(clrsdp_handle* h);
 int32_t clrsdp_restore_state(clrsdp_handle* h);
 
+/* Hand the iterate of one handle to another: x, X, y, Y of `src` are copied into `dst`, device
+ * to device (one kernel launch, no host staging).  The two handles may differ in
+ * precision_words, which is what the call is for: a solve can run at fp64 while that is good
+ * enough and continue at double-double or quad-double from the same iterate
+ * (solve_escalating).  Conversion per number, limbs moved as doubles without arithmetic:
+ *   dst as wide as src   a bitwise copy
+ *   dst wider            the source limbs followed by exact zeros (the same value)
+ *   dst narrower         the leading limbs; the library keeps its words renormalised
+ *                        (non-overlapping), so this is the value rounded to the narrower width
+ *                        (to nearest, up to the usual last-limb ambiguity of a renormalised sum)
+ * Ordering: the copy runs after the work already enqueued on src's stream and before anything
+ * enqueued later on dst's stream.  The call synchronises both streams (it is not meant for the
+ * loop's path), so src may be destroyed as soon as it returns.
+ * Afterwards dst is exactly as after clrsdp_set_state with the same values: the <X,Y> partials
+ * are refreshed and the next CORRECTOR_R sums its dot product itself; dst's buffers do not move,
+ * so its captured loop-body graphs stay valid; its scalar slots, constraints, control and
+ * factorisation flags are untouched (call clrsdp_initial_residuals next, as after set_state).
+ * Refusals copy nothing and change neither handle's state (clrsdp_last_error(dst) says why):
+ *   CLRSDP_E_ARG    a NULL handle; dst == src; different devices; different clrsdp_desc
+ *                   contents (J, n_y, m, L, n_samples, delta, ranks); different rank,
+ *                   world_size or owned set
+ *   CLRSDP_E_STATE  either handle has loop bodies in flight (clrsdp_iterate_async without its
+ *                   clrsdp_iterate_wait); src never had a state (clrsdp_set_state or a hand-off)
+ * A loop body that failed (CLRSDP_E_NOT_PD_X / _S / _Q, CLRSDP_E_STEP) applied no update, so src
+ * then still holds the state from before that body and can hand it over.
+ * (No reference counterpart: the reference runs one precision per solve.) */
+int32_t clrsdp_handoff_state(clrsdp_handle* dst, clrsdp_handle* src);
+
 /* Run all work on `stream` (a hipStream_t; NULL = the handle's own stream). */
 int32_t clrsdp_set_stream(clrsdp_handle* h, void* stream);
 void* clrsdp_get_stream(const clrsdp_handle* h);
