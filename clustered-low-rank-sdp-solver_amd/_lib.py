@@ -25,7 +25,8 @@ STAGE_NAMES = ["mu_R", "Xinv", "schur", "factor", "residuals", "predictor", "cor
                "corrector", "step", "update"]
 
 (BUF_X, BUF_Y, BUF_XINV, BUF_R, BUF_S, BUF_AY, BUF_Q, BUF_P, BUF_PVEC, BUF_DVEC, BUF_DX,
- BUF_DXMAT, BUF_DY, BUF_DYMAT, BUF_XVEC, BUF_YVEC, BUF_SCALARS) = range(17)
+ BUF_DXMAT, BUF_DY, BUF_DYMAT, BUF_XVEC, BUF_YVEC, BUF_SCALARS, BUF_LXINV, BUF_LQINV,
+ BUF_QINV) = range(20)
 
 SC = dict(mu=0, mu_p=1, r=2, beta=3, beta_c=4, mu_c=5, alpha_p=6, alpha_d=7, mineig_X=8,
           mineig_Y=9, p_obj=10, d_obj=11, err_P=12, err_p=13, err_d=14, dot_XY=15, dot_XdY=16,
@@ -41,7 +42,8 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_get_factorization", "clrsdp_set_graph", "clrsdp_comm_info", "clrsdp_eigmin",
            "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
            "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info",
-           "clrsdp_eigmin_kernel", "clrsdp_handoff_state"]
+           "clrsdp_eigmin_kernel", "clrsdp_handoff_state", "clrsdp_chol_spdinv",
+           "clrsdp_spdinv_kernel"]
 # clrsdp_eigmin_kernel codes (include/clrsdp.h)
 EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK = range(6)
 EIG_K_NAMES = {0: "eigmin_split", 1: "eigmin_mx", 2: "eigmin_lds2", 3: "eigmin_lds",
@@ -170,6 +172,9 @@ def lib():
     L.clrsdp_eigmin_kernel.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]
     L.clrsdp_getrf.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32, P_i32]
     L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]
+    L.clrsdp_chol_spdinv.argtypes = [C.c_int32, C.c_int64, P_i64, P_i64, P_i32, P_f64, P_f64, P_f64,
+                                     P_i32]
+    L.clrsdp_spdinv_kernel.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
     L.clrsdp_trsm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_i64,
                               P_f64, P_f64]
     L.clrsdp_gemm.argtypes = [C.c_int32] * 5 + [C.c_double, C.c_double, P_f64, C.c_double, C.c_int64,

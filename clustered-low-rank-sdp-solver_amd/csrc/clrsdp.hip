@@ -1190,27 +1190,51 @@ struct PermPlan : PlanBase {
 };
 
 template <class T>
-struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
-  std::vector<MatDesc<T>> hin, hout, hl;
-  MatDesc<T>*din = nullptr, *dout = nullptr, *dl = nullptr;
+struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b, or A_b^-1)
+  std::vector<MatDesc<T>> hin, hout, hl, hg;
+  MatDesc<T>*din = nullptr, *dout = nullptr, *dl = nullptr, *dg = nullptr;
+  // Whether a batch takes the form of chol_inv_tiles that also leaves A^-1 = L^-T L^-1 (the
+  // product formed in the factorisation's launch instead of a GEMM behind it): fp64 on-chip
+  // blocks up to 128, never where the inverse comes from the pivoted LU (lu_x() / lu_sq()), and
+  // CLRSDP_CHOL_SPDINV=0 (`sw` false) keeps the GEMM.
+  static bool spdinv_dispatch(int nmax, bool lu, bool sw) {
+    return std::is_same<T, double>::value && sw && !lu && nmax >= 1 && nmax <= 128;
+  }
   void add(T* A, int n, int lda, T* out, int ldo, T* L = nullptr) {
     hin.push_back(MatDesc<T>{A, n, lda});
     hout.push_back(MatDesc<T>{out, n, ldo});
     nmax = std::max(nmax, n);
     if (L) hl.push_back(MatDesc<T>{L, n, ldo});
   }
+  // A_b^-1 of the matrix added last into G (pitch ldg), which must not alias its input or its
+  // L^-1; matrices without one run the plain form.  Read by launch(.., true) only.
+  void want_inverse(T* G, int ldg) {
+    hg.resize(hin.size(), MatDesc<T>{nullptr, 0, 0});
+    hg.back() = MatDesc<T>{G, hin.back().n, ldg};
+  }
   void finalize() {
     if (hin.empty()) return;
     din = own(hin);
     dout = own(hout);
     if (!hl.empty()) dl = own(hl);
+    if (!hg.empty()) {
+      hg.resize(hin.size(), MatDesc<T>{nullptr, 0, 0});
+      dg = own(hg);
+    }
   }
   int nmax = 0;
-  void launch(hipStream_t s, int* info) const {
+  // spdinv: the matrices that asked for A^-1 (want_inverse) get it; the caller decides by
+  // spdinv_dispatch
+  void launch(hipStream_t s, int* info, bool spdinv = false) const {
     if (hin.empty()) return;
     const unsigned nb = (unsigned)hin.size();
     if constexpr (std::is_same<T, double>::value) {
-      if (nmax <= 32) go<32>(s, nb, info);
+      if (spdinv) {
+        if (!dg || nmax > 128) throw ClrsdpError{CLRSDP_E_ARG, "chol_inv_tiles with A^-1: n <= 128 and a target only"};
+        if (nmax <= 32) go<32, true>(s, nb, info);
+        else if (nmax <= 64) go<64, true>(s, nb, info);
+        else go<128, true>(s, nb, info);
+      } else if (nmax <= 32) go<32>(s, nb, info);
       else if (nmax <= 64) go<64>(s, nb, info);
       else if (nmax <= 128) go<128>(s, nb, info);
       else if (nmax <= 256) go<256>(s, nb, info);
@@ -1226,7 +1250,7 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
     }
     HIPCHK(hipGetLastError());
   }
-  template <int NP>
+  template <int NP, bool SPDINV = false>
   void go(hipStream_t s, unsigned nb, int* info) const {
     static_assert(sizeof(double) * CholTiles<NP>::END + sizeof(int) * CholTiles<NP>::NFLAGS <= LDS_MAX,
                   "chol_inv_tiles: LDS");
@@ -1235,10 +1259,10 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b)
     // streams' GEMM waves on the same SIMDs
     constexpr int prio = 1;
     static std::atomic<unsigned long long> attr{0};
-    lds_attr_once(attr, (const void*)chol_inv_tiles<NP>, (int)lds);
-    chol_inv_tiles<NP><<<nb, CholTiles<NP>::NTH, lds, s>>>(
+    lds_attr_once(attr, (const void*)chol_inv_tiles<NP, SPDINV>, (int)lds);
+    chol_inv_tiles<NP, SPDINV><<<nb, CholTiles<NP>::NTH, lds, s>>>(
         reinterpret_cast<const MatDesc<double>*>(din), reinterpret_cast<const MatDesc<double>*>(dout), info,
-        prio);
+        prio, SPDINV ? reinterpret_cast<const MatDesc<double>*>(dg) : nullptr);
   }
 };
 
@@ -1450,6 +1474,10 @@ struct Solver final : HandleBase {
   MatPlan<T> f_X, f_Y, f_S, f_Q, e_X, e_Y;
   // on-chip factorisation path (all sizes <= reg_nmax<T>()): L^-1 and MFMA products
   bool reg_blk = false, reg_S = false, reg_Q = false;
+  // fp64: chol_inv_tiles leaves X^-1 / Q^-1 beside L^-1 (CholInvPlan::spdinv_dispatch; without
+  // the LU fallback, which st_xinv / factor_q_ look at when they launch); CLRSDP_CHOL_SPDINV=0:
+  // the GEMMs q_xinv / p_xir and q_qinv behind the factorisation (per handle: tests switch it)
+  bool spd_xy = false, spd_q = false;
   CholInvPlan<T> ci_XY, ci_S, ci_S22, ci_Q;
   GemmPlan<T> q_xinv, q_sx1, q_sx2, q_sy1, q_sy2, q_W, q_t, q_Wdy, q_dx, q_q1, q_q2, q_qinv, q_qdy;
   // fp64, uniform blocks: Z, dY and the step-length products as one strip-chain launch each
@@ -1583,6 +1611,9 @@ struct Solver final : HandleBase {
   //   alpha_fused  set by st_step when it did so, cleared by the st_update that forms alpha
   //   xy_ov_body   set and cleared by enqueue_iteration beside fuse_alpha: the corrector's
   //                direction_rest may fork the X step length (it then signals h_stx)
+  //   r_late       set by st_xinv in a fuse_r body whose XINV is one launch (spd_xy: no GEMM to
+  //                carry R), cleared by enqueue_iteration, which forms R at the head of the side
+  //                stream's work after SCHUR
   //   head_ahead   set by enqueue_iteration (q_main) after solve_head ran on the side stream,
   //                cleared by the predictor's direction_solves, which then skips it
   //   dy_dot_ready set by the predictor's direction_rest when its dY chain left the
@@ -1590,7 +1621,7 @@ struct Solver final : HandleBase {
   //                set_state, restore_state)
   struct BodyFlags {
     bool fuse_r = false, fuse_alpha = false, alpha_fused = false, xy_ov_body = false,
-         head_ahead = false, dy_dot_ready = false;
+         head_ahead = false, dy_dot_ready = false, r_late = false;
   } body;
   float phase_ms[CLRSDP_NUM_STAGES];
 
@@ -1816,6 +1847,9 @@ struct Solver final : HandleBase {
       reg_blk = nmax_b <= reg_nmax<T>();
       reg_S = nmax_S <= (std::is_same<T, double>::value ? 2 : 1) * reg_nmax<T>();
       reg_Q = n_y <= reg_nmax<T>();
+      const bool spd_sw = !env_off("CLRSDP_CHOL_SPDINV");
+      spd_xy = reg_blk && nb() && CholInvPlan<T>::spdinv_dispatch(nmax_b, false, spd_sw);
+      spd_q = reg_Q && CholInvPlan<T>::spdinv_dispatch((int)n_y, false, spd_sw);
       // multi-word S_j / Q beyond the on-chip inverse: GEMV solves with L^-1 instead of the
       // serial multi-word vector solves (four 41-us trsv_wave chains per direction at C5), in the
       // split form: potrf on the critical path and L^-1 = L \ I by four-wave solves (S_j's beside
@@ -1869,6 +1903,8 @@ struct Solver final : HandleBase {
       f_X.add(LX + b.off, n, n);
       f_Y.add(LY + b.off, n, n);
       ci_XY.add(X + b.off, n, n, LX + b.off, n);
+      // (Xinv aliases neither X nor LX; the Y blocks below ask for no inverse)
+      if (spd_xy) ci_XY.want_inverse(Xinv + b.off, n);
       q_xinv.add(LX + b.off, n, LX + b.off, n, nullptr, n, Xinv + b.off, n, n, n, n);
       if constexpr (std::is_same<T, double>::value) {
         p_xir.add_op(true, false, 1.0, 0.0, LX + b.off, n, LX + b.off, n, nullptr, n, Xinv + b.off, n, n, n, n);
@@ -2167,6 +2203,7 @@ struct Solver final : HandleBase {
     t_dxadd_init();
     f_Q.add(Qf, (int)n_y, (int)n_y);
     ci_Q.add(Q, (int)n_y, (int)n_y, Qf, (int)n_y);
+    if (spd_q) ci_Q.want_inverse(Qinv, (int)n_y);  // (Qinv aliases neither Q nor Qf)
     q_q1.add(Qf, (int)n_y, dyv, (int)n_y, nullptr, 0, uvec, (int)n_y, (int)n_y, 1, (int)n_y);
     q_q2.add(Qf, (int)n_y, uvec, (int)n_y, nullptr, 0, dyv, (int)n_y, (int)n_y, 1, (int)n_y);
     // Q^-1 = L_Q^-T L_Q^-1 once per iteration (side stream), then one GEMV per direction
@@ -2948,10 +2985,14 @@ struct Solver final : HandleBase {
   }
   void st_xinv() {
     if (reg_blk) {  // L_X^-1 and L_Y^-1 on chip in one launch, X^-1 = L^-T L^-1 on MFMA
-      ci_XY.launch(stream, info);
+      // (spd_xy: X^-1 comes out of the same launch, and a loop body forms R on the side stream)
+      const bool spd = CholInvPlan<T>::spdinv_dispatch(ci_XY.nmax, lu_x(), spd_xy);
+      ci_XY.launch(stream, info, spd);
       if (lu_x()) {
         xinv_lu();
         if (body.fuse_r) mu_r_gemm();
+      } else if (spd) {
+        body.r_late = body.fuse_r;
       } else if (body.fuse_r) {
         p_xir.launch(stream, 1.0, 0.0);  // {X^-1 = L^-T L^-1 | R = mu_p I - XY}
       } else {
@@ -3163,8 +3204,9 @@ struct Solver final : HandleBase {
       return;
     }
     if (reg_Q) {
-      ci_Q.launch(stream, info + info_Q0);    // Qf = L_Q^-1
-      q_qinv.launch(stream, 1.0, 0.0);        // Q^-1 = L_Q^-T L_Q^-1
+      const bool spd = CholInvPlan<T>::spdinv_dispatch(ci_Q.nmax, lu_sq(), spd_q);
+      ci_Q.launch(stream, info + info_Q0, spd);  // Qf = L_Q^-1 (spd: and Q^-1 beside it)
+      if (!spd) q_qinv.launch(stream, 1.0, 0.0);  // Q^-1 = L_Q^-T L_Q^-1
     } else {
       if (!fresh) vlin(Qf, Q, 1.0, nullptr, 0, nullptr, 0, q2);
       f_Q.potrf(stream, info + info_Q0);
@@ -3660,6 +3702,8 @@ struct Solver final : HandleBase {
     // residuals; the right-hand side (U = Z V and its column sums) after FACTOR's side products
     // W1^T W1 and B2' (h_w), which are on the critical path to W2 = L22^-1 B2'
     fork(fev[EV_S], aux, [&] {
+      if (body.r_late) mu_r_gemm();  // R = mu_p I - XY, first read by Z below
+      body.r_late = false;
       if (p_late) residuals_P();
       direction_Z();
       residuals_rest(true);
@@ -4015,6 +4059,9 @@ struct Solver final : HandleBase {
       case CLRSDP_BUF_XVEC: src = x; n = nx; break;
       case CLRSDP_BUF_YVEC: src = y; n = n_y; break;
       case CLRSDP_BUF_SCALARS: src = sc; n = SC_COUNT; break;
+      case CLRSDP_BUF_LXINV: src = LX; n = nblk_el; break;
+      case CLRSDP_BUF_LQINV: src = Qf; n = n_y * n_y; break;
+      case CLRSDP_BUF_QINV: src = Qinv; n = n_y * n_y; break;
       default: throw ClrsdpError{CLRSDP_E_ARG, "bad buffer id"};
     }
     if (count) *count = n;
@@ -4205,6 +4252,48 @@ void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double
   static_assert(sizeof(int) == sizeof(int32_t), "info is 32-bit");
   HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
   download_planes<T>(inverse ? X : A, Ap, tot);
+}
+
+// L^-1 and (want[b]) A^-1 of fp64 blocks by one launch of CholInvPlan's SPDINV form; the output
+// buffers go to the device as the caller filled them, so what the kernel leaves alone comes back
+// unchanged
+static void chol_spdinv_f64(int device, int64_t nblk, const int64_t* n, const int64_t* ld, const int32_t* want,
+                     const double* Ap, double* Linv, double* Ainv, int32_t* info) {
+  std::vector<int64_t> off(nblk + 1, 0), ooff(nblk + 1, 0);
+  for (int64_t b = 0; b < nblk; ++b) {
+    off[b + 1] = off[b] + n[b] * n[b];
+    ooff[b + 1] = ooff[b] + (ld ? ld[b] : n[b]) * n[b];
+  }
+  DeviceGuard dg(device);
+  const int64_t tot = off[nblk], otot = ooff[nblk];
+  DevBuf mem;
+  double* A = mem.alloc<double>(tot);
+  double* X = mem.alloc<double>(otot);
+  double* G = Ainv ? mem.alloc<double>(otot) : nullptr;
+  int* dinfo = mem.alloc<int>(nblk);
+  HIPCHK(hipMemcpy(A, Ap, (size_t)tot * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(X, Linv, (size_t)otot * sizeof(double), hipMemcpyHostToDevice));
+  if (G) HIPCHK(hipMemcpy(G, Ainv, (size_t)otot * sizeof(double), hipMemcpyHostToDevice));
+  CholInvPlan<double> ci;
+  bool any = false;
+  for (int64_t b = 0; b < nblk; ++b) {
+    const int pitch = (int)(ld ? ld[b] : n[b]);
+    ci.add(A + off[b], (int)n[b], (int)n[b], X + ooff[b], pitch);
+    if (want && want[b]) {
+      ci.want_inverse(G + ooff[b], pitch);
+      any = true;
+    }
+  }
+  if (!any) ci.want_inverse(nullptr, 0);  // (a descriptor list of nulls: the same instance)
+  ci.finalize();
+  StreamOwner so;
+  ci.launch(so.s, dinfo, true);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so.s));
+  static_assert(sizeof(int) == sizeof(int32_t), "info is 32-bit");
+  HIPCHK(hipMemcpy(info, dinfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(Linv, X, (size_t)otot * sizeof(double), hipMemcpyDeviceToHost));
+  if (G) HIPCHK(hipMemcpy(Ainv, G, (size_t)otot * sizeof(double), hipMemcpyDeviceToHost));
 }
 
 // Triangular solves of each block at the word type T through TrsmPlan, as the solver runs them
@@ -5009,6 +5098,37 @@ int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nbl
     }
   }
   WORDS_CALL(potrf_words, device, inverse, nblocks, n, A, info)
+}
+
+int32_t clrsdp_chol_spdinv(int32_t device, int64_t nblocks, const int64_t* n, const int64_t* ld,
+                           const int32_t* want, const double* A, double* Linv, double* Ainv,
+                           int32_t* info) {
+  if (nblocks <= 0 || !n || !A || !Linv || !info) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
+  for (int64_t b = 0; b < nblocks; ++b) {
+    if (n[b] <= 0 || n[b] > 128) { g_last_error = "A^-1 on chip (chol_inv_tiles): 1 <= n <= 128 only"; return CLRSDP_E_ARG; }
+    if (ld && (ld[b] < n[b] || ld[b] > 4096)) { g_last_error = "pitch out of range"; return CLRSDP_E_ARG; }
+    if (want && want[b] && !Ainv) { g_last_error = "A^-1 asked for without a buffer"; return CLRSDP_E_ARG; }
+  }
+  try {
+    chol_spdinv_f64(device, nblocks, n, ld, want, A, Linv, Ainv, info);
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
+}
+
+int32_t clrsdp_spdinv_kernel(int32_t words, int64_t nmax, int32_t lu, int32_t* fused) {
+  if (!fused || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
+  const bool sw = !env_off("CLRSDP_CHOL_SPDINV");
+  if (words == 1) *fused = CholInvPlan<double>::spdinv_dispatch((int)nmax, lu != 0, sw);
+  else if (words == 2) *fused = CholInvPlan<mw::dd>::spdinv_dispatch((int)nmax, lu != 0, sw);
+  else if (words == 4) *fused = CholInvPlan<mw::qd>::spdinv_dispatch((int)nmax, lu != 0, sw);
+  else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  return CLRSDP_OK;
 }
 
 int32_t clrsdp_trsm(int32_t device, int32_t words, int32_t mode, int32_t trans, int64_t nblocks,

@@ -3304,14 +3304,42 @@ struct CholTiles {
     while (i * (i + 1) / 2 <= t) ++i;
     j = t - i * (i - 1) / 2;
   }
+  // The SPDINV form (chol_inv_tiles<NP, true>): the lower tiles of G = L^-T L^-1, diagonal ones
+  // included, row-major over GWK workers (tile t: G worker t mod GWK, slot t / GWK).
+  // CLRSDP_SPDINV_W4 = 0 keeps them off worker 3 (wave 4, which shares SIMD 0 with the chain
+  // wave); DESIGN.md section 6 has both times.
+#ifndef CLRSDP_SPDINV_W4
+#define CLRSDP_SPDINV_W4 1
+#endif
+  static constexpr int NG = NT * (NT + 1) / 2, GWK = CLRSDP_SPDINV_W4 ? NWK : NWK - 1;
+  static constexpr int GSLOTS = (NG + GWK - 1) / GWK;
+  static __device__ __forceinline__ int gworker(int wk) {  // index among the G workers, or -1
+    if (CLRSDP_SPDINV_W4) return wk;
+    return wk == 3 ? -1 : wk - (wk > 3);
+  }
+  static __device__ __forceinline__ void gtile(int t, int& i, int& j) {  // row-major, j <= i
+    i = 0;
+    while ((i + 1) * (i + 2) / 2 <= t) ++i;
+    j = t - i * (i + 1) / 2;
+  }
 };
 template <int NP>
 size_t chol_inv_tiles_lds() { return sizeof(double) * CholTiles<NP>::END + sizeof(int) * CholTiles<NP>::NFLAGS; }
 
-template <int NP>
+// SPDINV (NP <= 128): the workers also hold the lower tiles of G = A^-1 = L^-T L^-1 in GSLOTS more
+// accumulator slots.  In (c) of panel k, behind the trailing update, G_ij += X_ki^T X_kj for
+// i, j <= k, both operands read from the X row block in LDS (stable until the barrier that ends
+// (c)): the products grow with k as the trailing update shrinks.  After the last panel each tile
+// goes to out_g[block] with its mirror, so G is full and exactly symmetric; entries past n are
+// not written, and nothing of G is written for a block that fails.  A block whose out_g (or
+// out_g[block].A) is null runs the plain form's instructions on L and L^-1: those two come out
+// the same bits either way.  G must not alias the input or L^-1.
+template <int NP, bool SPDINV = false>
 __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDesc<double>* __restrict__ in,
                                                       const MatDesc<double>* __restrict__ out_inv,
-                                                      int* __restrict__ info, int prio = 0) {
+                                                      int* __restrict__ info, int prio = 0,
+                                                      const MatDesc<double>* __restrict__ out_g = nullptr) {
+  static_assert(!SPDINV || NP <= 128, "chol_inv_tiles: A^-1 in the accumulators for NP <= 128 only");
   using CT = CholTiles<NP>;
   // prio: the diagonal chain (wave 0) at priority 3, the workers at 2, above co-resident waves
   // of other launches (which stay at 0)
@@ -3459,12 +3487,40 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
     d4 XD[DSLOTS];
 #pragma unroll
     for (int q = 0; q < DSLOTS; ++q) XD[q] = d4{0.0, 0.0, 0.0, 0.0};
+    // ---- SPDINV: this worker's tiles of G (wave-uniform coordinates; row NT: an empty slot)
+    constexpr int GSLOTS = SPDINV ? CT::GSLOTS : 1;
+    double* gA = nullptr;
+    int ldg = 0;
+    if constexpr (SPDINV) {
+      if (out_g) {
+        gA = out_g[blockIdx.x].A;
+        ldg = out_g[blockIdx.x].lda;
+      }
+    }
+    int GI[GSLOTS], GJ[GSLOTS];
+    d4 G[GSLOTS];
+#pragma unroll
+    for (int q = 0; q < GSLOTS; ++q) {
+      int gi = NT, gj = 0;
+      if constexpr (SPDINV) {
+        const int gw = CT::gworker(wk);
+        const int t = gw + CT::GWK * q;
+        if (gA && gw >= 0 && t < CT::NG) CT::gtile(t, gi, gj);
+      }
+      GI[q] = gi;
+      GJ[q] = gj;
+      G[q] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+    bool done = true;
     prologue_load();
     prologue_store();
     lds_barrier();  // (the chain wave's first diagonal factor)
     CT_TRACE();
     for (int k = 0; k < nt; ++k) {
-      if (*FAIL(k)) break;
+      if (*FAIL(k)) {
+        done = false;
+        break;
+      }
       // an opaque zero per panel: the per-slot LDS and store addresses below are formed where
       // they are used, not hoisted out of the loop (NP = 256: dozens of loop-invariant
       // addresses kept live across the panels spilled to scratch)
@@ -3575,9 +3631,57 @@ __global__ __launch_bounds__(CholTiles<NP>::NTH) void chol_inv_tiles(const MatDe
 #pragma unroll
         for (int r = 0; r < 4; ++r) D[lr * LDD + lk + 4 * r] = acc[r];
       }
+      // SPDINV: G_ij += X_ki^T X_kj (i, j <= k), row block k of L^-1 as both MFMA operands
+      if constexpr (SPDINV) {
+#pragma unroll
+        for (int q = 0; q < GSLOTS; ++q) {
+          if (GI[q] > k) continue;
+          d4 acc = G[q];
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            acc = mfma64(Xr_[(4 * r + lk) * XLD + 16 * GI[q] + lr],
+                         Xr_[(4 * r + lk) * XLD + 16 * GJ[q] + lr], acc);
+          G[q] = acc;
+        }
+      }
       CT_TRACE();
       lds_barrier();
       CT_TRACE();
+    }
+    // SPDINV: register r of a G slot = G_ij[lk + 4r][lr], which is coalesced (16 lanes along a
+    // column) where the mirror (j, i) goes.  The tile itself goes out transposed through a
+    // 16 x 17 scratch of this worker's own in the panel / row-block buffers, which nobody reads
+    // after the last panel's barrier (no barrier here: a wave reads what it wrote).  A diagonal
+    // tile takes both halves from its lower one, so G is exactly symmetric.  Inside n x n only.
+    if constexpr (SPDINV) {
+      constexpr int GLD = 17;
+      static_assert((CT::NG + 1 < NWK ? CT::NG + 1 : NWK) * 16 * GLD <= NT * 256 + 16 * XLD,
+                    "chol_inv_tiles: the transposing scratch of the workers that hold G tiles");
+      if (done) {
+        double* S = Pn + wk * 16 * GLD;
+#pragma unroll
+        for (int q = 0; q < GSLOTS; ++q) {
+          if (GI[q] >= nt) continue;
+          double t[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) S[(lk + 4 * r) * GLD + lr] = G[q][r];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t[r] = S[lr * GLD + lk + 4 * r];  // G_ij[lr][lk + 4r]
+          const bool diag = GI[q] == GJ[q];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = lk + 4 * r;
+            const int gi = 16 * GI[q] + lr, gj = 16 * GJ[q] + c;  // (i, j): row lr, column c
+            const int mi = 16 * GJ[q] + lr, mj = 16 * GI[q] + c;  // (j, i): row lr, column c
+            if (diag) {
+              if (gi < n && gj < n) gA[gi + (size_t)gj * ldg] = lr >= c ? t[r] : G[q][r];
+            } else {
+              if (gi < n) gA[gi + (size_t)gj * ldg] = t[r];
+              if (mj < n) gA[mi + (size_t)mj * ldg] = G[q][r];
+            }
+          }
+        }
+      }
     }
   }
   if (tid == 0 && info) info[blockIdx.x] = flag[0] ? flag[0] : flag[3];

@@ -372,6 +372,49 @@ def eigmin_kernel(nmax: int, precision_words: int = 1) -> int:
     return k.value
 
 
+def spdinv_kernel(nmax: int, precision_words: int = 1, lu: bool = False) -> bool:
+    """Whether the XINV stage / chol(Q) of a batch whose largest block is ``nmax`` form the
+    inverse inside the factorisation's launch (True) or by a GEMM behind it, under the current
+    environment (clrsdp_spdinv_kernel: fp64 and nmax <= 128 only, never with the LU fallback
+    ``lu``; ``CLRSDP_CHOL_SPDINV=0`` keeps the GEMM).  A host-only query."""
+    k = C.c_int32(-1)
+    _lib.check(_lib.lib().clrsdp_spdinv_kernel(int(precision_words), int(nmax), 1 if lu else 0,
+                                               C.byref(k)))
+    return bool(k.value)
+
+
+def chol_spdinv(blocks, want=None, pitch=None, fill=np.nan, device: int = 0):
+    """``L^-1`` and, where ``want[b]``, ``A^-1 = L^-T L^-1`` of fp64 symmetric positive definite
+    blocks (n <= 128) from one launch of the factorisation kernel (clrsdp_chol_spdinv).  ``want``:
+    one flag per block (default: every block); ``pitch``: per block the leading dimension of both
+    outputs (default n).  Returns ``(Linv, Ainv, info)``: per block two arrays of shape
+    (pitch, n) that held ``fill`` in every entry before the launch, so what the kernel did not
+    write still holds it, and ``info`` as ``potrf(inverse=True)``."""
+    mats = [np.asarray(b, dtype=np.float64) for b in blocks]
+    for a in mats:
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("blocks must be square")
+    n = np.array([a.shape[0] for a in mats], dtype=np.int64)
+    ld = n.copy() if pitch is None else np.array(pitch, dtype=np.int64)
+    w = np.ones(len(mats), dtype=np.int32) if want is None else \
+        np.array([1 if f else 0 for f in want], dtype=np.int32)
+    if len(ld) != len(mats) or len(w) != len(mats):
+        raise ValueError("one pitch and one flag per block")
+    A = np.ascontiguousarray(np.concatenate([a.reshape(-1, order="F") for a in mats]))
+    tot = max(int((ld * n).sum()), 1)
+    Li = np.full(tot, fill, dtype=np.float64)
+    Gi = np.full(tot, fill, dtype=np.float64)
+    info = np.zeros(max(len(mats), 1), dtype=np.int32)
+    _lib.check(_lib.lib().clrsdp_chol_spdinv(device, len(mats), n.ctypes.data_as(_lib.P_i64),
+                                             ld.ctypes.data_as(_lib.P_i64),
+                                             w.ctypes.data_as(_lib.P_i32), _ptr(A), _ptr(Li),
+                                             _ptr(Gi), info.ctypes.data_as(_lib.P_i32)))
+    off = np.concatenate([[0], np.cumsum(ld * n)])
+    cut = lambda v, b: v[off[b]:off[b + 1]].reshape((ld[b], n[b]), order="F").copy()
+    return ([cut(Li, b) for b in range(len(mats))], [cut(Gi, b) for b in range(len(mats))],
+            info[:len(mats)].copy())
+
+
 def getrf(blocks, precision_words: int = 1, device: int = 0, raw_limbs: bool = False):
     """Partially pivoted LU of each square block, ``A[perm] = L U``, at fp64 / double-double /
     quad-double (clrsdp_getrf: approx_lu!, MPMP.jl:1436, 1501, as the solver's LU path runs it).

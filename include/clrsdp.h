@@ -84,6 +84,9 @@ extern "C" {
 #define CLRSDP_BUF_XVEC 14    /* x (local)                                                    */
 #define CLRSDP_BUF_YVEC 15    /* y (n_y)                                                      */
 #define CLRSDP_BUF_SCALARS 16 /* clrsdp_scalar slots (see CLRSDP_SC_*)                          */
+#define CLRSDP_BUF_LXINV 17   /* STAGE_XINV's factor buffer (blocks): L_X^-1 on the on-chip path */
+#define CLRSDP_BUF_LQINV 18   /* chol(Q)'s factor buffer (n_y^2): L_Q^-1 on the on-chip path    */
+#define CLRSDP_BUF_QINV 19    /* Q^-1 (n_y^2) where the Q solve uses it (fp64, n_y <= 128)      */
 #define CLRSDP_NUM_BUFS 17
 
 /* slots of CLRSDP_BUF_SCALARS */
@@ -461,6 +464,28 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
  * it.  After a failure that block's contents are unspecified; the other blocks are complete. */
 int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nblocks,
                      const int64_t* n, double* A, int32_t* info);
+
+/* L_b^-1 and, for the blocks that ask, A_b^-1 = L_b^-T L_b^-1 of fp64 symmetric positive definite
+ * blocks in ONE launch of the form of chol_inv_tiles that keeps the tiles of A^-1 in its
+ * accumulators (the XINV stage's launch, and chol(Q)'s).  A: nblocks blocks of sizes n[]
+ * (1 <= n[b] <= 128) concatenated column-major, pitch n[b]; only lower triangles are read.
+ * Linv and Ainv: block b is n[b] columns of pitch ld[b] >= n[b] (ld null: pitch n[b]), blocks
+ * concatenated; both are copied to the device before the launch and back after it, so an entry
+ * the kernel does not write returns as it came.  Linv_b receives L_b^-1 (exact zeros above the
+ * diagonal), the same bits whether or not A_b^-1 is asked for.  want[b] != 0: Ainv_b receives
+ * the full, exactly symmetric A_b^-1; want[b] = 0, or a block that fails: Ainv_b is not written
+ * (want null: no block asks, Ainv may be null).  Rows past n[b] of a column are never written.
+ * info as clrsdp_potrf with inverse = 1. */
+int32_t clrsdp_chol_spdinv(int32_t device, int64_t nblocks, const int64_t* n, const int64_t* ld,
+                           const int32_t* want, const double* A, double* Linv, double* Ainv,
+                           int32_t* info);
+
+/* Whether a batch of on-chip factorisations with the inverse whose largest block is nmax, at
+ * `words`, takes that form (*fused = 1) or the plain one with the product L^-T L^-1 as a GEMM
+ * behind it (0), under the current environment (CLRSDP_CHOL_SPDINV): fp64 and nmax <= 128 only,
+ * and never when the inverse comes from the pivoted LU (lu != 0: CLRSDP_FACT_LU_X for X,
+ * CLRSDP_FACT_LU_SQ for Q).  A host-only query: no device is touched. */
+int32_t clrsdp_spdinv_kernel(int32_t words, int64_t nmax, int32_t lu, int32_t* fused);
 
 /* Triangular solves of each block in place on B_b (n[b] x nrhs[b]), as the solver runs them
  * (approx_solve_tril! / approx_solve_triu!, MPMP.jl:1457-1460, 1751-1773): trsm_batched (the
