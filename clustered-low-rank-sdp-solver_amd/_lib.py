@@ -43,11 +43,11 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
            "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info",
            "clrsdp_eigmin_kernel", "clrsdp_handoff_state", "clrsdp_chol_spdinv",
-           "clrsdp_spdinv_kernel"]
+           "clrsdp_spdinv_kernel", "clrsdp_eigmin_routes"]
 # clrsdp_eigmin_kernel codes (include/clrsdp.h)
-EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK = range(6)
+EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK, EIG_K_MXBLK = range(7)
 EIG_K_NAMES = {0: "eigmin_split", 1: "eigmin_mx", 2: "eigmin_lds2", 3: "eigmin_lds",
-               4: "eigmin_batched", 5: "eigblk chain"}
+               4: "eigmin_batched", 5: "eigblk chain", 6: "mxblk route"}
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -169,6 +169,8 @@ def lib():
     L.clrsdp_comm_info.argtypes = [C.c_void_p, P_i32, P_i32]
     L.clrsdp_schur_info.argtypes = [C.c_void_p, C.POINTER(SchurInfo)]
     L.clrsdp_eigmin.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_f64]
+    L.clrsdp_eigmin_routes.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_f64,
+                                       C.POINTER(C.c_int32)]
     L.clrsdp_eigmin_kernel.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]
     L.clrsdp_getrf.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32, P_i32]
     L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]

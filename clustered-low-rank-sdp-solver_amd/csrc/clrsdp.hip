@@ -910,7 +910,127 @@ struct MatPlan : PlanBase {  // potrf / eigmin
     }
     if (!std::is_same<T, double>::value) redo = own(std::vector<int>(h.size(), 1));
     eig_blk = use == Use::EIG_ONLY && env_on("CLRSDP_EIG_BLK");
-    if (eig_dispatch(nmax, eig_blk) == CLRSDP_EIG_K_BLK) finalize_eig_chain();
+    eig_mxblk = use == Use::EIG_ONLY && mxblk_on();
+    const int ek = eig_dispatch(nmax, eig_blk, eig_mxblk);
+    // the flagged blocks of the mxblk route go to the route the switch replaced; where
+    // eigmin_batched would ask for more LDS than a launch gets unasked (it then cannot run
+    // today either), to the multi-word chain
+    mx_fb_chain = ek == CLRSDP_EIG_K_MXBLK && (eig_blk || batched_lds(nmax) > 64 * 1024);
+    if (ek == CLRSDP_EIG_K_BLK || mx_fb_chain) finalize_eig_chain();
+    if (ek == CLRSDP_EIG_K_MXBLK) finalize_mxblk();
+  }
+  static size_t batched_lds(int n) { return sizeof(T) * (4 * (size_t)n + 256); }  // eigmin_batched
+  bool mx_fb_chain = false;
+  // ---- multi-word lambda_min of blocks past the LDS kernels from a refined fp64 eigenpair
+  // (mxblk_*, kernels_dense.h).  CLRSDP_EIG_MX_BLK=1 (off with CLRSDP_EIG_MX=0): a multi-word
+  // batch that eigmin() would give to eigmin_batched (or, with CLRSDP_EIG_BLK=1, to the
+  // multi-word chain) first goes through the fp64 chain, the fp64 Cholesky chain and a few
+  // refinement steps at the word's width; the blocks Temple's bound does not certify are
+  // flagged in `redo`, and the route the switch replaced then runs on those alone.  Read when
+  // the plan is finalised, where all of its scratch is allocated.  Opt-in: DESIGN.md §1.
+  static bool mxblk_on() { return env_on("CLRSDP_EIG_MX_BLK") && !env_off("CLRSDP_EIG_MX"); }
+  // the first size of the route per word type: the first of eigmin_batched's range (the route
+  // was ahead of both older routes there)
+  static constexpr int MXBLK_NMIN = std::is_same<T, mw::dd>::value ? 97 : 67;
+  static constexpr int MXBLK_NMAX = 4096;  // the 2^-40 margin of lam2 covers n 2^-52 up to here
+  bool eig_mxblk = false;
+  MxBlkDesc<T>* md = nullptr;
+  EigBlkDesc<double>* ed64 = nullptr;
+  BlkPotrfDesc<double>* bd64 = nullptr;
+  int* info64 = nullptr;
+  double* lam64 = nullptr;
+  double* mx_st = nullptr;  // MXBLK_ST state words per block
+  TrsmPlan<double> mx_ts;   // the vector solves with the factor of A_h - mu I
+  // tools/micro/eig_mxblk_bench: three events recorded behind the fp64 chain with its Sturm
+  // step, the factor, and the inverse iteration (null in the library: a capture records none)
+  hipEvent_t* mx_phase_ev = nullptr;
+  void finalize_mxblk() {
+    if constexpr (!std::is_same<T, double>::value) {
+      constexpr int R = EIG_R;
+      const size_t nm = h.size();
+      size_t sq = 0, vec = 0, parts = 0, words = 0;
+      for (const MatDesc<T>& m : h) {
+        sq += (size_t)m.n * m.n;
+        vec += m.n;
+        parts += cdiv(m.n, R);
+        words += eigblk_ws_words(m.n);
+      }
+      double* Ah = own(std::vector<double>(sq, 0.0));
+      double* Af = own(std::vector<double>(sq, 0.0));
+      double* zb = own(std::vector<double>(2 * vec, 0.0));
+      T* xy = own(std::vector<T>(2 * vec, T(0.0)));
+      double* am = own(std::vector<double>(2 * parts, 0.0));
+      double* ws = own(std::vector<double>(words, 0.0));
+      mx_st = own(std::vector<double>(nm * MXBLK_ST, 0.0));
+      lam64 = own(std::vector<double>(nm, 0.0));
+      info64 = own(std::vector<int>(nm, 0));
+      std::vector<MxBlkDesc<T>> m(nm);
+      std::vector<EigBlkDesc<double>> e(nm);
+      std::vector<BlkPotrfDesc<double>> b(nm);
+      sq = vec = parts = words = 0;
+      for (size_t q = 0; q < nm; ++q) {
+        const int n = h[q].n;
+        m[q] = MxBlkDesc<T>{h[q].A, Ah + sq, Af + sq, am + 2 * parts, zb + 2 * vec, zb + 2 * vec + n,
+                            xy + 2 * vec, xy + 2 * vec + n, mx_st + q * MXBLK_ST, n, h[q].lda};
+        e[q] = EigBlkDesc<double>{Ah + sq, ws + words, am + 2 * parts + cdiv(n, R), n, n};
+        b[q] = BlkPotrfDesc<double>{Af + sq, nullptr, n, n};
+        mx_ts.add(Af + sq, n, zb + 2 * vec + n, n, n, 1);
+        sq += (size_t)n * n;
+        vec += n;
+        parts += cdiv(n, R);
+        words += eigblk_ws_words(n);
+      }
+      md = own(m);
+      ed64 = own(e);
+      bd64 = own(b);
+      mx_ts.finalize();
+      // every instance that can ask for more than 64 KiB of dynamic LDS, outside any capture
+      static std::atomic<unsigned long long> ac{0}, as{0};
+      lds_attr_once(ac, (const void*)eigblk_col<double, EIG_R>, (int)LDS_MAX);
+      lds_attr_once(as, (const void*)mxblk_sturm<T>, (int)LDS_MAX);
+    }
+  }
+  // the launches of the route up to the flags; eigmin() follows with the flagged blocks
+  void eigmin_mxblk(hipStream_t s, T* out) const {
+    if constexpr (!std::is_same<T, double>::value) {
+      constexpr int R = EIG_R, NB = BLK64_NB;
+      const unsigned nm = (unsigned)h.size();
+      const dim3 strips(cdiv(nmax, R), nm);
+      mxblk_amax<T, R><<<strips, 64, 0, s>>>(md);
+      mxblk_image<T, R><<<strips, 64, 0, s>>>(md);
+      eigblk_amax<double, R><<<strips, 64, 0, s>>>(ed64);
+      eigblk_sym<double, R><<<strips, 64, 0, s>>>(ed64);
+      const size_t lds = eigblk_col_lds<double>(nmax);
+      for (int k = 0; k + 2 < nmax; ++k)
+        eigblk_col<double, R><<<dim3(cdiv(nmax - k - 1, R), nm), 64, lds, s>>>(ed64, k);
+      mxblk_sturm<T><<<nm, 512, mxblk_sturm_lds(nmax), s>>>(ed64, md, lam64);
+      HIPCHK(hipGetLastError());
+      if (mx_phase_ev) HIPCHK(hipEventRecord(mx_phase_ev[0], s));
+      potrf64_first<NB><<<nm, 256, 0, s>>>(bd64, info64);
+      for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
+        const int rows = nmax - k0 - NB, nch = cdiv(rows, 64);
+        potrf64_trsm<NB><<<dim3((unsigned)nch, nm), 64, 0, s>>>(bd64, k0, info64);
+        potrf64_update<NB><<<dim3(1u + (unsigned)(nch * (nch + 1) / 2), nm), 256, 0, s>>>(bd64, k0, info64);
+      }
+      HIPCHK(hipGetLastError());
+      if (mx_phase_ev) HIPCHK(hipEventRecord(mx_phase_ev[1], s));
+      for (int r = 0; r < MXBLK_INVIT; ++r) {
+        mx_ts.launch(s, false);
+        mx_ts.launch(s, true);
+        mxblk_norm<T><<<nm, 256, 0, s>>>(md, info64, r == 0, r + 1 == MXBLK_INVIT);
+      }
+      if (mx_phase_ev) HIPCHK(hipEventRecord(mx_phase_ev[2], s));
+      for (int it = 0; it <= MXBLK_REFINE; ++it) {
+        mxblk_matvec<T><<<strips, 256, 0, s>>>(md);
+        mxblk_rayleigh<T><<<nm, 256, 0, s>>>(md, out, it, it == MXBLK_REFINE);
+        if (it == MXBLK_REFINE) break;
+        mx_ts.launch(s, false);
+        mx_ts.launch(s, true);
+        mxblk_update<T><<<nm, 256, 0, s>>>(md);
+      }
+      mxblk_finish<T><<<cdiv(nm, 256), 256, 0, s>>>(md, (int)nm, redo);
+      HIPCHK(hipGetLastError());
+    }
   }
   // ---- lambda_min of blocks past the LDS kernels across workgroups (eigblk_*, kernels_dense.h)
   // CLRSDP_EIG_BLK=1: a batch that eigmin() would give to the one-CU eigmin_batched goes to the
@@ -926,8 +1046,8 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // the largest n whose v_k and w (eigblk_col's dynamic LDS) fit one CU
   static constexpr int eig_chain_nmax() { return (int)(LDS_MAX / (2 * sizeof(T))); }
   // The kernel eigmin() launches for a batch whose largest block is nmax (CLRSDP_EIG_K_*,
-  // clrsdp.h), `chain` being CLRSDP_EIG_BLK as the plan read it
-  static int eig_dispatch(int nmax, bool chain) {
+  // clrsdp.h), `chain` being CLRSDP_EIG_BLK and `mxblk` CLRSDP_EIG_MX_BLK as the plan read them
+  static int eig_dispatch(int nmax, bool chain, bool mxblk = false) {
     if (std::is_same<T, double>::value && nmax <= 128) return CLRSDP_EIG_K_SPLIT;  // matrix in registers
     if (!std::is_same<T, double>::value) {
       // n <= 64: an fp64 eigenpair refined at the word's width (eigmin_mx; the blocks it cannot
@@ -941,6 +1061,8 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       if (eig2_lds_bytes<T>(nmax) <= LDS_MAX && (sizeof(T) <= 16 || nmax <= 64)) return CLRSDP_EIG_K_LDS2;
     }
     if (eig_lds_bytes<T>(nmax) <= LDS_MAX) return CLRSDP_EIG_K_LDS;
+    if (!std::is_same<T, double>::value && mxblk && nmax >= MXBLK_NMIN && nmax <= MXBLK_NMAX)
+      return CLRSDP_EIG_K_MXBLK;
     return chain ? CLRSDP_EIG_K_BLK : CLRSDP_EIG_K_BATCHED;
   }
   void finalize_eig_chain() {
@@ -970,16 +1092,17 @@ struct MatPlan : PlanBase {  // potrf / eigmin
     lds_attr_once(at, (const void*)eigblk_sturm<T, true>, (int)LDS_MAX);
     lds_attr_once(ag, (const void*)eigblk_sturm<T, false>, (int)LDS_MAX);
   }
-  void eigmin_chain(hipStream_t s, T* out) const {
+  // (flags: the fallback behind eigmin_mxblk, on the blocks with flags[block] != 0 only)
+  void eigmin_chain(hipStream_t s, T* out, const int* flags = nullptr) const {
     constexpr int R = EIG_R;
     const unsigned nm = (unsigned)h.size();
-    eigblk_amax<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed);
-    eigblk_sym<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed);
+    eigblk_amax<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed, flags);
+    eigblk_sym<T, R><<<dim3(cdiv(nmax, R), nm), 64, 0, s>>>(ed, flags);
     const size_t lds = eigblk_col_lds<T>(nmax);
     for (int k = 0; k + 2 < nmax; ++k)
-      eigblk_col<T, R><<<dim3(cdiv(nmax - k - 1, R), nm), 64, lds, s>>>(ed, k);
-    if (eig_tri) eigblk_sturm<T, true><<<nm, 512, eigblk_sturm_lds<T>(nmax, true), s>>>(ed, out, R);
-    else eigblk_sturm<T, false><<<nm, 512, eigblk_sturm_lds<T>(nmax, false), s>>>(ed, out, R);
+      eigblk_col<T, R><<<dim3(cdiv(nmax - k - 1, R), nm), 64, lds, s>>>(ed, k, flags);
+    if (eig_tri) eigblk_sturm<T, true><<<nm, 512, eigblk_sturm_lds<T>(nmax, true), s>>>(ed, out, R, flags);
+    else eigblk_sturm<T, false><<<nm, 512, eigblk_sturm_lds<T>(nmax, false), s>>>(ed, out, R, flags);
     HIPCHK(hipGetLastError());
   }
   void potrf(hipStream_t s, int* info) const {
@@ -1041,7 +1164,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   void eigmin(hipStream_t s, T* out) const {
     if (h.empty()) return;
     const unsigned nm = (unsigned)h.size();
-    switch (eig_dispatch(nmax, eig_blk)) {
+    switch (eig_dispatch(nmax, eig_blk, eig_mxblk)) {
       case CLRSDP_EIG_K_SPLIT:
         if constexpr (std::is_same<T, double>::value) {
           // eigmin_split: one reflector chain wave + 8 bulk waves, the last 24 columns on the
@@ -1083,6 +1206,15 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       case CLRSDP_EIG_K_BLK:
         eigmin_chain(s, out);
         return;
+      case CLRSDP_EIG_K_MXBLK:
+        // the flagged blocks by the route the switch replaced; the others exit at once
+        eigmin_mxblk(s, out);
+        if (mx_fb_chain) {
+          eigmin_chain(s, out, redo);
+          return;
+        }
+        eigmin_batched<T><<<nm, 256, batched_lds(nmax), s>>>(d, out, redo);
+        break;
       default:  // CLRSDP_EIG_K_BATCHED
         eigmin_batched<T><<<nm, 256, sizeof(T) * (4 * (size_t)nmax + 256), s>>>(d, out);
         break;
@@ -4168,7 +4300,8 @@ void download_planes(const T* d, double* planes, int64_t cnt) {
 // lambda_min of each symmetric block at the word type T (the eigenvalue part of
 // compute_step_length, MPMP.jl:1857-1870): planes in, planes out
 template <class T>
-void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, double* ep) {
+void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, double* ep,
+                  int32_t* route = nullptr) {
   DeviceGuard dg(device);
   std::vector<int64_t> off(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) {
@@ -4186,6 +4319,27 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(so.s));
   download_planes<T>(eig, ep, nblk);
+  if (!route) return;
+  // per block: 0 certified by the refinement, 1 flagged and computed by the fallback launch;
+  // -1 for a batch whose kernel has no certification step
+  const int ek = MatPlan<T>::eig_dispatch(eg.nmax, eg.eig_blk, eg.eig_mxblk);
+  if ((ek != CLRSDP_EIG_K_MX && ek != CLRSDP_EIG_K_MXBLK) || !eg.redo) {
+    for (int64_t b = 0; b < nblk; ++b) route[b] = -1;
+    return;
+  }
+  static_assert(sizeof(int) == sizeof(int32_t), "the flags are 32-bit");
+  HIPCHK(hipMemcpy(route, eg.redo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+  if (ek == CLRSDP_EIG_K_MXBLK && env_on("CLRSDP_EIGMX_STATS")) {
+    std::vector<double> st((size_t)nblk * MXBLK_ST);
+    HIPCHK(hipMemcpy(st.data(), eg.mx_st, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    int flagged = 0, steps = 0;
+    for (int64_t b = 0; b < nblk; ++b) {
+      flagged += route[b] != 0;
+      if (route[b] == 0) steps = std::max(steps, (int)st[(size_t)b * MXBLK_ST + 6]);
+    }
+    std::fprintf(stderr, "clrsdp: eigmin_mxblk: %d of %lld blocks flagged, most refinement steps of a certified block %d\n",
+                 flagged, (long long)nblk, steps);
+  }
 }
 
 // Pivoted LU of each block at the word type T through LuPlan, as the solver's LU path runs it
@@ -5044,10 +5198,10 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
 
 int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel) {
   if (!kernel || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
-  const bool chain = env_on("CLRSDP_EIG_BLK");
+  const bool chain = env_on("CLRSDP_EIG_BLK"), mxblk = MatPlan<mw::dd>::mxblk_on();
   if (words == 1) *kernel = MatPlan<double>::eig_dispatch((int)nmax, chain);
-  else if (words == 2) *kernel = MatPlan<mw::dd>::eig_dispatch((int)nmax, chain);
-  else if (words == 4) *kernel = MatPlan<mw::qd>::eig_dispatch((int)nmax, chain);
+  else if (words == 2) *kernel = MatPlan<mw::dd>::eig_dispatch((int)nmax, chain, mxblk);
+  else if (words == 4) *kernel = MatPlan<mw::qd>::eig_dispatch((int)nmax, chain, mxblk);
   else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
   return CLRSDP_OK;
 }
@@ -5072,6 +5226,13 @@ int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int6
   if (nblocks <= 0 || !n || !A || !min_eig) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
   if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
   WORDS_CALL(eigmin_words, device, nblocks, n, A, min_eig)
+}
+
+int32_t clrsdp_eigmin_routes(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
+                             const double* A, double* min_eig, int32_t* route) {
+  if (nblocks <= 0 || !n || !A || !min_eig || !route) { g_last_error = "null argument or no blocks"; return CLRSDP_E_ARG; }
+  if (words != 1 && words != 2 && words != 4) { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  WORDS_CALL(eigmin_words, device, nblocks, n, A, min_eig, route)
 }
 
 int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64_t* n, double* A,
@@ -5273,12 +5434,13 @@ int32_t clrsdp_get_factorization(const clrsdp_handle* h, int32_t* flags) {
 
 int32_t clrsdp_destroy(clrsdp_handle* h) {
   if (!h) return CLRSDP_OK;
-  // CLRSDP_EIGMX_STATS=1: how many blocks eigmin_mx handed to the multi-word path so far (all
-  // handles of the process; diagnostics only)
+  // CLRSDP_EIGMX_STATS=1: how many blocks eigmin_mx and the mxblk route handed to the multi-word
+  // path so far (all handles of the process; diagnostics only)
   if (env_on("CLRSDP_EIGMX_STATS")) {
-    unsigned int fb = 0;
-    if (hipMemcpyFromSymbol(&fb, HIP_SYMBOL(g_eigmx_fallbacks), sizeof(fb)) == hipSuccess)
-      std::fprintf(stderr, "clrsdp: eigmin_mx multi-word fallbacks so far: %u\n", fb);
+    unsigned int fb = 0, ms = 0;
+    if (hipMemcpyFromSymbol(&fb, HIP_SYMBOL(g_eigmx_fallbacks), sizeof(fb)) == hipSuccess &&
+        hipMemcpyFromSymbol(&ms, HIP_SYMBOL(g_mxblk_steps), sizeof(ms)) == hipSuccess)
+      std::fprintf(stderr, "clrsdp: eigmin_mx multi-word fallbacks so far: %u (mxblk route: most refinement steps %u)\n", fb, ms);
     std::vector<double> z(256 * 24);
     if (hipMemcpyFromSymbol(z.data(), HIP_SYMBOL(g_eigmx_dbg), z.size() * sizeof(double)) == hipSuccess)
       for (int b = 0; b < 64; ++b) {

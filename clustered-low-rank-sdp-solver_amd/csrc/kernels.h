@@ -2235,8 +2235,10 @@ __device__ __forceinline__ int sturm_count(const T* dg, const T* e2, int n, T si
 
 template <class T>
 __global__ __launch_bounds__(256) void eigmin_batched(const MatDesc<T>* __restrict__ descs,
-                                                      T* __restrict__ out) {
+                                                      T* __restrict__ out,
+                                                      const int* __restrict__ redo = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  if (redo && redo[blockIdx.x] == 0) return;  // (a fallback launch: the flagged blocks only)
   const MatDesc<T> d = descs[blockIdx.x];
   const int n = d.n, lda = d.lda, tid = threadIdx.x;
   T* v = reinterpret_cast<T*>(smem_raw);  // n

@@ -2279,7 +2279,9 @@ template <class T> constexpr size_t eigblk_sturm_lds(int n, bool tri) {
 }
 
 template <class T, int R>
-__global__ __launch_bounds__(64) void eigblk_amax(const EigBlkDesc<T>* __restrict__ descs) {
+__global__ __launch_bounds__(64) void eigblk_amax(const EigBlkDesc<T>* __restrict__ descs,
+                                                  const int* __restrict__ redo = nullptr) {
+  if (redo && redo[blockIdx.y] == 0) return;  // (a fallback launch: the flagged blocks only)
   const EigBlkDesc<T> d = descs[blockIdx.y];
   const int n = d.n, lane = threadIdx.x, i = blockIdx.x * R + lane;
   if ((int)blockIdx.x * R >= n) return;
@@ -2300,7 +2302,9 @@ __device__ __forceinline__ int eigblk_exp(const EigBlkDesc<T>& d, int R) {
 }
 
 template <class T, int R>
-__global__ __launch_bounds__(64) void eigblk_sym(const EigBlkDesc<T>* __restrict__ descs) {
+__global__ __launch_bounds__(64) void eigblk_sym(const EigBlkDesc<T>* __restrict__ descs,
+                                                 const int* __restrict__ redo = nullptr) {
+  if (redo && redo[blockIdx.y] == 0) return;
   const EigBlkDesc<T> d = descs[blockIdx.y];
   const int n = d.n, lda = d.lda, lane = threadIdx.x, i = blockIdx.x * R + lane;
   if ((int)blockIdx.x * R >= n) return;
@@ -2322,8 +2326,10 @@ __global__ __launch_bounds__(64) void eigblk_sym(const EigBlkDesc<T>* __restrict
 }
 
 template <class T, int R>
-__global__ __launch_bounds__(64) void eigblk_col(const EigBlkDesc<T>* __restrict__ descs, int k) {
+__global__ __launch_bounds__(64) void eigblk_col(const EigBlkDesc<T>* __restrict__ descs, int k,
+                                                 const int* __restrict__ redo = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  if (redo && redo[blockIdx.y] == 0) return;
   const EigBlkDesc<T> d = descs[blockIdx.y];
   const int n = d.n, lda = d.lda, lane = threadIdx.x;
   if (n <= k + 2) return;
@@ -2433,8 +2439,10 @@ __global__ __launch_bounds__(64) void eigblk_col(const EigBlkDesc<T>* __restrict
 // in global memory through the same pointers (2n words past the CU's LDS)
 template <class T, bool TRI>
 __global__ __launch_bounds__(512) void eigblk_sturm(const EigBlkDesc<T>* __restrict__ descs,
-                                                    T* __restrict__ out, int R) {
+                                                    T* __restrict__ out, int R,
+                                                    const int* __restrict__ redo = nullptr) {
   extern __shared__ __attribute__((aligned(32))) char smem_raw[];
+  if (redo && redo[blockIdx.x] == 0) return;
   const EigBlkDesc<T> d = descs[blockIdx.x];
   const int n = d.n, lda = d.lda, tid = threadIdx.x;
   T* scr = reinterpret_cast<T*>(smem_raw);
@@ -3104,6 +3112,330 @@ __global__ __launch_bounds__(TRI ? 576 : 512) void eigmin_mx(const MatDesc<T>* _
     redo[blockIdx.x] = ok ? 0 : 1;
     if (!ok && n >= 3) atomicAdd(&g_eigmx_fallbacks, 1u);
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// mxblk_*: eigmin_mx's scheme for multi-word blocks past the LDS kernels (CLRSDP_EIG_MX_BLK=1,
+// in place of eigmin_batched / the multi-word eigblk_* chain): the O(n^3) work is fp64 and
+// spread over workgroups, the multi-word work is one n^2 matrix-vector product per refinement
+// step.  No reflectors are kept (the fp64 eigblk_* chain forms only the tridiagonal), so the
+// correction operator is the dense fp64 Cholesky factor of A_h - mu I with mu just below lambda.
+// The multi-word block A is only read; every fp64 image lives in the plan's scratch.  Per batch:
+//   mxblk_amax     per strip of R rows, the largest leading-limb magnitude of A (Inf for a strip
+//                  that holds a NaN or Inf)
+//   mxblk_image    ex = pow2_exp(max of the partials); two fp64 images of the leading limbs of
+//                  A_s = (A + A^T) / 2^(ex + 1); a block with n < 3, all zeros or a non-finite
+//                  entry is flagged here (its images are the identity)
+//   eigblk_amax / _sym / _col<double>  on the first image: its tridiagonal
+//   mxblk_sturm    the pending update of the last 2 x 2 and the multisection of eigblk_sturm for
+//                  lambda; a lower bound lam2 of lambda_2 from one round of full Sturm counts at
+//                  lambda + span 2^(-t/4) (t < 256), less 2^-40 of the Gershgorin magnitude
+//                  (eigmin_mx's rule: it covers the n 2^-52 between T and A_s up to n = 4096);
+//                  mu = lambda - max(2^-40, 16 n 2^-53) span, subtracted from the second image's
+//                  diagonal; the starting right-hand side of the inverse iteration
+//   potrf64_*      Cholesky of the second image (a failed block is flagged, not an error)
+//   MXBLK_INVIT x [trsm forward, trsm transposed, mxblk_norm]: z by inverse iteration,
+//                  normalised after every round; x = z at the word's width after the last
+//   at most MXBLK_REFINE + 1 x [mxblk_matvec, mxblk_rayleigh, trsm, trsm, mxblk_update]:
+//     matvec       y = A_s x at the word's width: 64 rows per workgroup, four waves with a fixed
+//                  quarter of the columns each (ascending), combined as (q0 + q1) + (q2 + q3)
+//     rayleigh     rho = x^T y / x^T x, r = y - rho x, eta = |r|^2 / |x|^2; Temple: rho is accepted
+//                  when eta / (lam2 - rho) <= 2^-(BITS+2) of the magnitude, and out = rho 2^ex;
+//                  flagged when no lam2 lies above rho or the last step was not accepted;
+//                  otherwise the fp64 right-hand side P (-r 2^k), P = I - z z^T, k from max |r|
+//     update       x += P d 2^-k at the word's width, d the solution of the two vector solves
+//   mxblk_finish   redo[block] = 0 for an accepted block, 1 for a flagged one: the launch of
+//                  the multi-word route that follows takes the flagged blocks only
+// The state of a block (state[7]: 0 running, 1 accepted, 2 flagged) lives on the device, and a
+// block that is no longer running leaves every mxblk launch at once (the vector solves run on
+// its stale right-hand side, which nothing reads).  Every sum is one thread's ascending sum or a
+// fixed tree over a fixed thread -> element map, one workgroup per block: lambda_min does not
+// depend on the grid or on the rest of the batch.  Launch arguments are constant, nothing waits
+// inside a launch and nothing is read back, so the sequence can be captured.
+// ------------------------------------------------------------------------------------------
+// refinement steps at most.  Started at 8; every certified block of tests/test_gpu_eig_mxblk.py
+// took 1 (double-double) or 2 (quad-double), the CPU restatement of the scheme 3 at most (gap
+// 2^-20 at 212 bits).  Every step's launches are enqueued whether or not a block still runs
+// (nothing is read back), so the spare steps cost launches: 4 keeps one in hand.
+constexpr int MXBLK_REFINE = 4;
+constexpr int MXBLK_INVIT = 3;   // rounds of inverse iteration for z
+constexpr int MXBLK_ST = 8;      // state words: lambda, lam2, mu, magnitude, ex, k, steps, state
+__device__ unsigned int g_mxblk_steps = 0;  // most refinement steps of an accepted block so far
+template <class T>
+struct MxBlkDesc {
+  const T* A;    // n x n, leading dimension lda (read only)
+  double* Ah;    // n x n, ld n: the image the fp64 chain tridiagonalises (destroyed by it)
+  double* Af;    // n x n, ld n: the image that becomes the factor of A_h - mu I
+  double* amax;  // one partial per strip of the prepass
+  double* z;     // n   the fp64 eigenvector
+  double* b;     // n   right-hand side / solution of the vector solves
+  T* x;          // n   the eigenvector estimate at the word's width
+  T* y;          // n   A_s x
+  double* st;    // MXBLK_ST words of state
+  int n, lda;
+};
+constexpr size_t mxblk_sturm_lds(int n) { return eigblk_sturm_lds<double>(n, true) + 512 * sizeof(double); }
+
+template <class T, int R>
+__global__ __launch_bounds__(64) void mxblk_amax(const MxBlkDesc<T>* __restrict__ descs) {
+  const MxBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lane = threadIdx.x, i = blockIdx.x * R + lane;
+  if ((int)blockIdx.x * R >= n) return;
+  double amax = 0.0;
+  if (lane < R && i < n)
+    for (int j = 0; j < n; ++j) {
+      const double a = fabs(Num<T>::hi(d.A[i + (size_t)j * d.lda]));
+      amax = a < INFINITY ? fmax(amax, a) : INFINITY;  // (NaN: not below Inf either)
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+  if (lane == 0) d.amax[blockIdx.x] = amax;
+}
+
+template <class T, int R>
+__global__ __launch_bounds__(64) void mxblk_image(const MxBlkDesc<T>* __restrict__ descs) {
+  const MxBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lda = d.lda, lane = threadIdx.x, i = blockIdx.x * R + lane;
+  if ((int)blockIdx.x * R >= n) return;
+  double mx = 0.0;
+  for (int s = 0; s * R < n; ++s) mx = fmax(mx, d.amax[s]);
+  const bool bad = !(mx > 0.0 && mx < INFINITY) || n < 3;
+  const int ex = bad ? 0 : pow2_exp(mx);
+  if (blockIdx.x == 0 && lane == 0) {
+    d.st[4] = (double)ex;
+    d.st[5] = 0.0;
+    d.st[6] = 0.0;
+    d.st[7] = bad ? 2.0 : 0.0;
+  }
+  if (lane >= R || i >= n) return;
+  // the thread of row i owns the pairs (i, j), (j, i) with j <= i
+  const T* A = d.A;
+  for (int j = 0; j <= i; ++j) {
+    double h = i == j ? 1.0 : 0.0;
+    if (!bad) {
+      const T a = scale2(A[i + (size_t)j * lda], -ex);
+      h = Num<T>::hi(i == j ? a : (a + scale2(A[j + (size_t)i * lda], -ex)) * T(0.5));
+    }
+    d.Ah[i + (size_t)j * n] = h;
+    d.Ah[j + (size_t)i * n] = h;
+    d.Af[i + (size_t)j * n] = h;
+    d.Af[j + (size_t)i * n] = h;
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(512) void mxblk_sturm(const EigBlkDesc<double>* __restrict__ edescs,
+                                                   const MxBlkDesc<T>* __restrict__ mdescs,
+                                                   double* __restrict__ lamv) {
+  extern __shared__ __attribute__((aligned(32))) char smem_raw[];
+  const EigBlkDesc<double> d = edescs[blockIdx.x];
+  const MxBlkDesc<T> m = mdescs[blockIdx.x];
+  const int n = d.n, lda = d.lda, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (m.st[7] != 0.0) return;  // flagged by the prepass (n >= 3 from here on)
+  double* scr = reinterpret_cast<double*>(smem_raw);
+  double* Wv = reinterpret_cast<double*>(smem_raw + eigblk_sturm_scr(n));
+  double* dl = Wv + 1;
+  double* el = dl + n;
+  double* red = reinterpret_cast<double*>(smem_raw + eigblk_sturm_lds<double>(n, true));  // 512
+  double* dgg = d.ws + 2 * (2 * (size_t)n + 1);
+  double* e2g = dgg + n;
+  if (tid == 0) {
+    // reflector n - 3 is pending on the last 2 x 2 (eigblk_sturm)
+    const double* A = d.A;
+    const double* vp = eigblk_state(d, (n - 2) & 1);
+    const double* pp = vp + n;
+    const int r0 = n - 2, r1 = n - 1;
+    const double v0 = vp[r0], v1 = vp[r1];
+    const double Kc = vp[2 * n] * (pp[r0] * v0 + pp[r1] * v1) * 0.5;
+    const double w0 = pp[r0] - Kc * v0, w1 = pp[r1] - Kc * v1;
+    dgg[r0] = (A[r0 + (size_t)r0 * lda] - v0 * w0) - w0 * v0;
+    dgg[r1] = (A[r1 + (size_t)r1 * lda] - v1 * w1) - w1 * v1;
+    const double e = (A[r1 + (size_t)r0 * lda] - v1 * w0) - w1 * v0;
+    e2g[r0] = e * e;
+  }
+  __syncthreads();
+  for (int q = tid; q < n; q += 512) {
+    dl[q] = dgg[q];
+    el[q] = q + 1 < n ? e2g[q] : 0.0;
+  }
+  __syncthreads();
+  eig_multisection<double, true>(dl, el, n, scr, Wv, lamv, 0);
+  __syncthreads();
+  const double lam = lamv[blockIdx.x];
+  // Gershgorin bracket of the tridiagonal
+  double glo = INFINITY, ghi = -INFINITY;
+  for (int i = tid; i < n; i += 512) {
+    const double rr = (i > 0 ? sqrt(el[i - 1]) : 0.0) + (i + 1 < n ? sqrt(el[i]) : 0.0);
+    glo = fmin(glo, dl[i] - rr);
+    ghi = fmax(ghi, dl[i] + rr);
+  }
+  glo = -block_max(-glo, red);
+  ghi = block_max(ghi, red);
+  const double span = ghi - glo, mag = fmax(fabs(glo), fabs(ghi));
+  // lower bound of lambda_2: the largest lam + span 2^(-t/4) (t < 256) with at most one
+  // eigenvalue of T below it
+  unsigned long long* masks = reinterpret_cast<unsigned long long*>(red);
+  bool le1 = false;
+  if (tid < 256) le1 = sturm_count_piv(dl, el, n, lam + span * exp2(-(double)tid * 0.25)) <= 1;
+  const unsigned long long mk = __ballot(le1);
+  if (lane == 0) masks[w] = mk;
+  __syncthreads();
+  int f2 = -1;
+  for (int q = 0; q < 4 && f2 < 0; ++q)
+    if (masks[q]) f2 = q * 64 + __ffsll((long long)masks[q]) - 1;
+  const bool fin = mag > 0.0 && mag < INFINITY && lam == lam;
+  const double lam2 = f2 < 0 ? -INFINITY : lam + span * exp2(-(double)f2 * 0.25) - 0x1p-40 * mag;
+  const double mu = lam - fmax(0x1p-40, 16.0 * (double)n * 0x1p-53) * span;
+  for (int i = tid; i < n; i += 512) {
+    m.Af[i + (size_t)i * n] -= mu;
+    // a fixed start with no symmetry of its own (a vector of ones is orthogonal to the wanted
+    // eigenvector of many structured blocks)
+    const double g = (double)(i + 1) * 0.6180339887498949;
+    m.b[i] = 0.5 + (g - floor(g));
+  }
+  if (tid == 0) {
+    m.st[0] = lam;
+    m.st[1] = lam2;
+    m.st[2] = mu;
+    m.st[3] = mag;
+    if (!fin || f2 < 0) m.st[7] = 2.0;  // no lambda_2 bound: Temple's bound cannot hold
+  }
+}
+
+// z = b / |b| after a round of inverse iteration, b = z for the next round; after the last
+// round x = z at the word's width
+template <class T>
+__global__ __launch_bounds__(256) void mxblk_norm(const MxBlkDesc<T>* __restrict__ descs,
+                                                  const int* __restrict__ info, int first, int last) {
+  __shared__ double red[256];
+  const MxBlkDesc<T> d = descs[blockIdx.x];
+  const int n = d.n, tid = threadIdx.x;
+  if (d.st[7] != 0.0) return;
+  if (first && info[blockIdx.x] != 0) {  // A_h - mu I did not factor
+    if (tid == 0) d.st[7] = 2.0;
+    return;
+  }
+  double mx = 0.0;
+  bool fin = true;
+  for (int i = tid; i < n; i += 256) {
+    const double a = fabs(d.b[i]);
+    fin = fin && a < INFINITY;
+    mx = fmax(mx, a);
+  }
+  mx = block_max(mx, red);
+  const double nf = block_max(fin ? 0.0 : 1.0, red);
+  if (nf != 0.0 || !(mx > 0.0)) {
+    if (tid == 0) d.st[7] = 2.0;
+    return;
+  }
+  double s = 0.0;
+  for (int i = tid; i < n; i += 256) {
+    const double v = d.b[i] / mx;
+    s += v * v;
+  }
+  const double nrm = sqrt(block_sum(s, red));
+  for (int i = tid; i < n; i += 256) {
+    const double v = (d.b[i] / mx) / nrm;
+    d.z[i] = v;
+    d.b[i] = v;
+    if (last) d.x[i] = T(v);
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void mxblk_matvec(const MxBlkDesc<T>* __restrict__ descs) {
+  __shared__ T part[3 * 64];
+  const MxBlkDesc<T> d = descs[blockIdx.y];
+  const int n = d.n, lda = d.lda, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if ((int)blockIdx.x * 64 >= n) return;
+  if (d.st[7] != 0.0) return;
+  const int ex = (int)d.st[4];
+  const int i = blockIdx.x * 64 + lane, ic = min(i, n - 1);
+  const int cq = (n + 3) / 4, j0 = w * cq, j1 = min(n, j0 + cq);
+  const T* __restrict__ A = d.A;
+  const T* __restrict__ x = d.x;
+  T acc = T(0.0);
+#pragma unroll 2
+  for (int j = j0; j < j1; ++j) {
+    const T a1 = scale2(A[ic + (size_t)j * lda], -ex), a2 = scale2(A[j + (size_t)ic * lda], -ex);
+    acc = acc + ((a1 + a2) * T(0.5)) * x[j];
+  }
+  if (w > 0) part[(w - 1) * 64 + lane] = acc;
+  __syncthreads();
+  if (w == 0 && i < n) d.y[i] = (acc + part[lane]) + (part[64 + lane] + part[128 + lane]);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void mxblk_rayleigh(const MxBlkDesc<T>* __restrict__ descs,
+                                                      T* __restrict__ out, int it, int last) {
+  __shared__ T red[256];
+  __shared__ double redd[256];
+  const MxBlkDesc<T> d = descs[blockIdx.x];
+  const int n = d.n, tid = threadIdx.x;
+  if (d.st[7] != 0.0) return;
+  T num = T(0.0), den = T(0.0);
+  for (int i = tid; i < n; i += 256) {
+    const T xi = d.x[i];
+    num = num + xi * d.y[i];
+    den = den + xi * xi;
+  }
+  num = block_sum(num, red);
+  den = block_sum(den, red);
+  const T rho = num / den;
+  double e = 0.0, rm = 0.0;
+  for (int i = tid; i < n; i += 256) {
+    const double rh = Num<T>::hi(d.y[i] - rho * d.x[i]);
+    e += rh * rh;
+    rm = fmax(rm, fabs(rh));
+  }
+  const double eta = block_sum(e, redd) / Num<T>::hi(den);
+  rm = block_max(rm, redd);
+  const double lam2 = d.st[1], mag = d.st[3], rhs = Num<T>::hi(rho);
+  const double tw = lam2 > rhs ? eta / (lam2 - rhs) : INFINITY;
+  const bool acc = tw <= ldexp(mag, -(Num<T>::BITS + 2));
+  if (acc || last || !(lam2 > rhs)) {
+    if (tid == 0) {
+      if (acc) {
+        out[blockIdx.x] = scale2(rho, (int)d.st[4]);
+        d.st[6] = (double)it;
+      }
+      d.st[7] = acc ? 1.0 : 2.0;
+    }
+    return;
+  }
+  // the right-hand side of the correction: P (-r 2^k) in fp64
+  const int k = -pow2_exp(rm);
+  double c = 0.0;
+  for (int i = tid; i < n; i += 256)
+    c += d.z[i] * -ldexp(Num<T>::hi(d.y[i] - rho * d.x[i]), k);
+  c = block_sum(c, redd);
+  for (int i = tid; i < n; i += 256)
+    d.b[i] = -ldexp(Num<T>::hi(d.y[i] - rho * d.x[i]), k) - c * d.z[i];
+  if (tid == 0) d.st[5] = (double)k;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void mxblk_update(const MxBlkDesc<T>* __restrict__ descs) {
+  __shared__ double red[256];
+  const MxBlkDesc<T> d = descs[blockIdx.x];
+  const int n = d.n, tid = threadIdx.x;
+  if (d.st[7] != 0.0) return;
+  const int k = (int)d.st[5];
+  double c = 0.0;
+  for (int i = tid; i < n; i += 256) c += d.z[i] * d.b[i];
+  c = block_sum(c, red);
+  for (int i = tid; i < n; i += 256) d.x[i] = d.x[i] + T(ldexp(d.b[i] - c * d.z[i], -k));
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void mxblk_finish(const MxBlkDesc<T>* __restrict__ descs, int nm,
+                                                    int* __restrict__ redo) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nm) return;
+  const bool ok = descs[q].st[7] == 1.0;
+  redo[q] = ok ? 0 : 1;
+  if (ok) atomicMax(&g_mxblk_steps, (unsigned int)descs[q].st[6]);
+  else if (descs[q].n >= 3) atomicAdd(&g_eigmx_fallbacks, 1u);
 }
 
 }  // namespace clrsdp

@@ -342,11 +342,13 @@ def compute_step_length(M, dM, gamma, device: int = 0, return_eigs: bool = False
     return alpha.value, False
 
 
-def eigmin(blocks, precision_words: int = 1, device: int = 0):
+def eigmin(blocks, precision_words: int = 1, device: int = 0, return_routes: bool = False):
     """lambda_min of each exactly symmetric block at fp64 / double-double / quad-double
     (clrsdp_eigmin; the eigenvalue part of compute_step_length, MPMP.jl:1857-1870).  Blocks are
     float arrays or object arrays of mpmath numbers (split exactly into limbs); returns floats
-    (words 1) or mpmath numbers (the exact limb sums)."""
+    (words 1) or mpmath numbers (the exact limb sums).  With ``return_routes`` (clrsdp_eigmin_routes)
+    also one int per block: 0 certified by the refinement of eigmin_mx / the mxblk route, 1 flagged
+    by it and computed by the fallback launch, -1 the batch's kernel has no certification step."""
     w = int(precision_words)
     mats = [np.asarray(b) for b in blocks]
     for a in mats:
@@ -356,17 +358,25 @@ def eigmin(blocks, precision_words: int = 1, device: int = 0):
     flat = np.concatenate([a.reshape(-1, order="F") for a in mats])
     planes = to_planes(flat, w)
     out = np.zeros(w * len(mats))
-    _lib.check(_lib.lib().clrsdp_eigmin(device, w, len(mats), n.ctypes.data_as(_lib.P_i64),
-                                        _ptr(planes), _ptr(out)))
-    if w == 1:
-        return out
-    return from_planes(out, len(mats), w)
+    routes = np.zeros(len(mats), dtype=np.int32)
+    if return_routes:
+        _lib.check(_lib.lib().clrsdp_eigmin_routes(device, w, len(mats), n.ctypes.data_as(_lib.P_i64),
+                                                   _ptr(planes), _ptr(out),
+                                                   routes.ctypes.data_as(C.POINTER(C.c_int32))))
+    else:
+        _lib.check(_lib.lib().clrsdp_eigmin(device, w, len(mats), n.ctypes.data_as(_lib.P_i64),
+                                            _ptr(planes), _ptr(out)))
+    eig = out if w == 1 else from_planes(out, len(mats), w)
+    return (eig, routes) if return_routes else eig
 
 
 def eigmin_kernel(nmax: int, precision_words: int = 1) -> int:
     """Which kernel ``eigmin`` (and the STEP stage's eigen launches) takes for a batch whose largest
     block is ``nmax``, under the current environment: one of ``_lib.EIG_K_*``
-    (clrsdp_eigmin_kernel; a host-only query, no device and no launch)."""
+    (clrsdp_eigmin_kernel; a host-only query, no device and no launch).  ``EIG_K_MXBLK`` (6)
+    stands in eigmin_batched's multi-word range with ``CLRSDP_EIG_MX_BLK=1`` (unless
+    ``CLRSDP_EIG_MX=0``): the fp64 eigenpair refined at the word's width across workgroups, then
+    the flagged blocks by the route the switch replaced."""
     k = C.c_int32(-1)
     _lib.check(_lib.lib().clrsdp_eigmin_kernel(int(precision_words), int(nmax), C.byref(k)))
     return k.value

@@ -411,9 +411,24 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
  * across workgroups with one launch per column, the multisection of eigmin_lds follows, and
  * lambda_min of a block is bitwise independent of the rest of the batch.  Its bound is the two
  * on-chip vectors of a column step, 2 nmax words in 160 KiB: beyond this entry point's 4096 at
- * fp64 and double-double, nmax <= 2560 at quad-double (larger: CLRSDP_E_ARG). */
+ * fp64 and double-double, nmax <= 2560 at quad-double (larger: CLRSDP_E_ARG).
+ * CLRSDP_EIG_MX_BLK=1 (environment, read when the call builds its plan; default off, and off
+ * with CLRSDP_EIG_MX=0) sends every multi-word batch of eigmin_batched's range through the
+ * mxblk_* route first, eigmin_mx's scheme across workgroups: the fp64 eigblk_* chain on the
+ * leading limbs, an fp64 Cholesky factor of A_h - mu I as the correction operator, and a few
+ * refinement steps at the word's width (one n^2 matrix-vector product each), accepted by
+ * Temple's bound.  The blocks it cannot certify (a multiple or tightly clustered lambda_min,
+ * n < 3) are flagged and go to the route the switch replaced -- eigmin_batched, or the
+ * multi-word chain with CLRSDP_EIG_BLK=1 or where eigmin_batched's request passes 64 KiB --
+ * in a second, flagged launch.  fp64 batches never take it. */
 int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
                       const double* A, double* min_eig);
+
+/* clrsdp_eigmin plus, per block, how lambda_min was obtained: route[b] = 0 certified by the
+ * refinement step of the batch's kernel (eigmin_mx, the mxblk_* route); 1 flagged by it and
+ * computed by the fallback launch; -1 the batch's kernel has no certification step. */
+int32_t clrsdp_eigmin_routes(int32_t device, int32_t words, int64_t nblocks, const int64_t* n,
+                             const double* A, double* min_eig, int32_t* route);
 
 /* Which kernel clrsdp_eigmin (and the STEP stage's eigen launches) takes for a batch at `words`
  * whose largest block is nmax (1 .. 4096), under the current environment.  A host-only query:
@@ -424,6 +439,7 @@ int32_t clrsdp_eigmin(int32_t device, int32_t words, int64_t nblocks, const int6
 #define CLRSDP_EIG_K_LDS 3      /* eigmin_lds                                                */
 #define CLRSDP_EIG_K_BATCHED 4  /* eigmin_batched (one workgroup per block, global memory)   */
 #define CLRSDP_EIG_K_BLK 5      /* eigblk_* chain across workgroups (CLRSDP_EIG_BLK=1)       */
+#define CLRSDP_EIG_K_MXBLK 6    /* mxblk_* route, then the flagged blocks (CLRSDP_EIG_MX_BLK=1) */
 int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel);
 
 /* Partially pivoted LU of each block in place, A_b[perm_b] = L_b U_b (approx_lu!, MPMP.jl:1436,
