@@ -43,7 +43,11 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_getrf", "clrsdp_trsm", "clrsdp_potrf", "clrsdp_gemm", "clrsdp_gemm_chain",
            "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info",
            "clrsdp_eigmin_kernel", "clrsdp_handoff_state", "clrsdp_chol_spdinv",
-           "clrsdp_spdinv_kernel", "clrsdp_eigmin_routes"]
+           "clrsdp_spdinv_kernel", "clrsdp_eigmin_routes", "clrsdp_apply_operator",
+           "clrsdp_cl_solve"]
+# clrsdp_apply_operator ops and the modes of its LIN op (include/clrsdp.h)
+APPLY_RHS, APPLY_WEIGHTED, APPLY_SYM, APPLY_LIN = range(4)
+LIN_COPY, LIN_SUB, LIN_DIAG = range(3)
 # clrsdp_eigmin_kernel codes (include/clrsdp.h)
 EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK, EIG_K_MXBLK = range(7)
 EIG_K_NAMES = {0: "eigmin_split", 1: "eigmin_mx", 2: "eigmin_lds2", 3: "eigmin_lds",
@@ -121,6 +125,12 @@ class SchurInfo(C.Structure):
                                          "s_lower")]
 
 
+class Operands(C.Structure):
+    _fields_ = [("blocks", P_f64), ("blocks2", P_f64), ("tuples", P_f64), ("scalar", P_f64),
+                ("mult", C.c_double), ("mode", C.c_int32), ("only_m", C.c_int32),
+                ("blocks_out", P_f64), ("tuples_out", P_f64)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p)
 
 _lib = None
@@ -196,6 +206,8 @@ def lib():
                                                                  C.c_int32, P_f64, P_f64]
     L.clrsdp_step_length.argtypes = [C.c_int32, C.c_int64, P_i64, P_f64, P_f64, C.c_double, P_f64,
                                      P_f64]
+    L.clrsdp_apply_operator.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Operands), P_i32]
+    L.clrsdp_cl_solve.argtypes = [C.c_int32, C.c_int64, P_i64, C.c_int64] + [P_f64] * 7
     for name in EXPORTS:
         if name not in ("clrsdp_last_error", "clrsdp_get_stream"):
             getattr(L, name).restype = C.c_int32

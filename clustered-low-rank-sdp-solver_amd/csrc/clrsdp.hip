@@ -1529,6 +1529,7 @@ struct HandleBase {
   virtual void set_graph(int on) = 0;
   virtual void comm_info(int* nranks, int* backend) const = 0;
   virtual void schur_info(struct clrsdp_schur_info* out) const = 0;
+  virtual void apply_operator(int op, const clrsdp_operands* a, int32_t* route) = 0;
 };
 
 template <class T>
@@ -2352,11 +2353,10 @@ struct Solver final : HandleBase {
       // summing four partial slabs per cluster 13.7 against 9.0 us: 1195-1232 against 1248-1270
       // it/s, A/B round 5 -- fewer workgroups with longer load chains lose to more, shorter ones)
       const bool cl_env = env_on("CLRSDP_CL_SOLVE");  // (per handle: tests switch it)
-      const long long cnt = (long long)std::max(nc(), 1) * std::max(cls_nrb, 1);
-      cls_on = cl_env && std::is_same<T, double>::value && reg_S && reg_Q && nc() > 0 &&
-               cls_nrb <= 4 && (long long)cdiv(n_y, 64) * cnt * n_y <= (1LL << 20) &&
-               ((size_t)n_y + 256) * sizeof(double) <= 64 * 1024;
-      for (const ClSolveDesc& cs : h_cls) cls_on = cls_on && cs.D <= 256;
+      int max_D = 0;
+      for (const ClSolveDesc& cs : h_cls) max_D = std::max(max_D, cs.D);
+      cls_on = cl_env && std::is_same<T, double>::value && reg_S && reg_Q &&
+               cl_solve_ok(nc(), cls_nrb, max_D, n_y);
       if (cls_on) d_cls = descs.own(h_cls);
     }
     if (nc()) {
@@ -3423,6 +3423,10 @@ struct Solver final : HandleBase {
     // Z is only consumed by trace_A: v^T Z v = v^T sym(Z) v, so the symmetrisation
     // (MPMP.jl:1704-1716) matters only for the off-diagonal (r != s) blocks of m > 1
     if (anyMgt1) sym(Z, Z, 0);
+    trace_products_Z_();
+  }
+  // U = Z V for trace_A (also what clrsdp_apply_operator's RHS runs on a Z given as it is)
+  void trace_products_Z_() {
     if (!c_trZ.on) p_trU_Z.launch(stream, 1.0, 0.0);  // (else U stays on chip, direction_rhs_)
   }
   // rhs_x = -d - Tr(A_* Z)   (MPMP.jl:1733-1739)
@@ -3493,12 +3497,11 @@ struct Solver final : HandleBase {
     }
     if constexpr (std::is_same<T, double>::value) {
       if (cls_on) {  // t and the partial slabs | dy = Q^-1 (p - sum) | u and dx: three launches
-        const unsigned g = (unsigned)(nc() * cls_nrb);
-        cl_solve_t<<<g, 256, 0, stream>>>(d_cls, cls_nrb, (int)n_y, pslab);
+        launch_cl_solve_t(stream, d_cls, nc(), cls_nrb, (int)n_y, pslab);
         const auto [src, cnt] = gather_slabs(pslab, nc() * cls_nrb, n_y, tag);  // (cls_on: nc() > 0)
         h_q.join(stream);
         launch_slab_qsolve(stream, src, cnt, n_y, (int)n_y, pvec, 1.0, -1.0, Qinv, (int)n_y, dyv);
-        cl_solve_dx<<<g, 256, 0, stream>>>(d_cls, cls_nrb, (int)n_y, dyv);
+        launch_cl_solve_dx(stream, d_cls, nc(), cls_nrb, (int)n_y, dyv);
         HIPCHK(hipGetLastError());
         return;
       }
@@ -4205,6 +4208,116 @@ struct Solver final : HandleBase {
         for (int64_t j = 0; j < D; ++j)
           for (int64_t i = 0; i < j; ++i) Sc[i + j * D] = Sc[j + i * D];
       }
+    }
+  }
+
+  // ---------------- the low-rank operators and block kernels on operands the caller gives
+  // (clrsdp_apply_operator): raw limbs into the work buffers, the loop body's own methods with
+  // its own descriptors and plans, raw limbs back.  Limbs are bit copies (a NaN keeps its payload).
+  void put_raw(T* dst, const double* planes, int64_t n) {
+    if (n <= 0) return;
+    constexpr int Wd = Num<T>::W;
+    std::vector<double> h((size_t)n * Wd);
+    for (int q = 0; q < Wd; ++q)
+      for (int64_t e = 0; e < n; ++e)
+        std::memcpy(&h[(size_t)e * Wd + q], &planes[(size_t)q * n + e], sizeof(double));
+    HIPCHK(hipMemcpyAsync(dst, h.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  void get_raw(const T* src, double* planes, int64_t n) {
+    if (n <= 0) return;
+    constexpr int Wd = Num<T>::W;
+    std::vector<double> h((size_t)n * Wd);
+    HIPCHK(hipMemcpyAsync(h.data(), src, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int q = 0; q < Wd; ++q)
+      for (int64_t e = 0; e < n; ++e)
+        std::memcpy(&planes[(size_t)q * n + e], &h[(size_t)e * Wd + q], sizeof(double));
+  }
+  void apply_operator(int op, const clrsdp_operands* a, int32_t* route) override {
+    static_assert(sizeof(T) == Num<T>::W * sizeof(double), "limb structs");
+    if (!uploaded) throw ClrsdpError{CLRSDP_E_STATE, "apply_operator: constraints not uploaded"};
+    if (inflight) throw ClrsdpError{CLRSDP_E_STATE, "apply_operator with loop bodies in flight"};
+    auto need = [](const void* p, const char* what) {
+      if (!p) throw ClrsdpError{CLRSDP_E_ARG, std::string("apply_operator: ") + what + " is NULL"};
+    };
+    need(route, "route");
+    switch (op) {
+      case CLRSDP_APPLY_RHS: {
+        need(a->blocks, "blocks (Z)");
+        need(a->tuples, "tuples (d)");
+        need(a->tuples_out, "tuples_out (rhs)");
+        put_raw(Z, a->blocks, nblk_el);
+        put_raw(dvec, a->tuples, nx);
+        put_raw(rhs, a->tuples_out, nx);
+        trace_products_Z_();
+        direction_rhs_();
+        *route = c_trZ.on ? 0 : trivial_tuples ? 1 : 2;
+        HIPCHK(hipGetLastError());
+        get_raw(rhs, a->tuples_out, nx);
+        break;
+      }
+      case CLRSDP_APPLY_WEIGHTED: {
+        need(a->tuples, "tuples (a)");
+        need(a->blocks, "blocks (the base)");
+        need(a->blocks_out, "blocks_out");
+        put_raw(dx, a->tuples, nx);
+        put_raw(P, a->blocks, nblk_el);
+        put_raw(dX, a->blocks_out, nblk_el);
+        weighted_A(dx, p_wA_dX, dX, 1.0);
+        *route = wa_fused ? 0 : 1;
+        HIPCHK(hipGetLastError());
+        get_raw(dX, a->blocks_out, nblk_el);
+        break;
+      }
+      case CLRSDP_APPLY_SYM: {
+        need(a->blocks, "blocks");
+        need(a->blocks_out, "blocks_out");
+        if (a->mode < 0 || a->mode > 2) throw ClrsdpError{CLRSDP_E_ARG, "apply_operator: SYM mode must be 0, 1 or 2"};
+        const bool only_m = a->only_m != 0;
+        put_raw(Z, a->blocks, nblk_el);
+        T* out = Z;  // modes 0 and 1 run in place, as sym(dY, dY, 0) and weighted_A's mirror do
+        if (a->mode == 2) {
+          out = tA;
+          put_raw(tA, a->blocks_out, nblk_el);
+        }
+        sym(out, Z, a->mode, only_m);
+        *route = (!only_m && std::is_same<T, double>::value && a->mode == 0 && nb() && sym_pairs) ? 0 : 1;
+        HIPCHK(hipGetLastError());
+        get_raw(out, a->blocks_out, nblk_el);
+        break;
+      }
+      case CLRSDP_APPLY_LIN: {
+        need(a->blocks, "blocks");
+        need(a->blocks_out, "blocks_out");
+        if (a->mode == CLRSDP_LIN_COPY) {          // as LX = X before a factorisation
+          put_raw(Z, a->blocks, nblk_el);
+          put_raw(tA, a->blocks_out, nblk_el);
+          blk_lin(tA, Z, 1.0, nullptr, 0.0);
+          HIPCHK(hipGetLastError());
+          get_raw(tA, a->blocks_out, nblk_el);
+        } else if (a->mode == CLRSDP_LIN_SUB) {    // as P = P - C
+          need(a->blocks2, "blocks2");
+          put_raw(P, a->blocks, nblk_el);
+          put_raw(tB, a->blocks2, nblk_el);
+          blk_lin(P, P, 1.0, tB, -1.0);
+          HIPCHK(hipGetLastError());
+          get_raw(P, a->blocks_out, nblk_el);
+        } else if (a->mode == CLRSDP_LIN_DIAG) {   // as R += mu I at multi-word
+          need(a->scalar, "scalar");
+          put_raw(R, a->blocks, nblk_el);
+          put_raw(tmpsc, a->scalar, 1);
+          blk_lin(R, R, 1.0, nullptr, 0.0, tmpsc, a->mult);
+          HIPCHK(hipGetLastError());
+          get_raw(R, a->blocks_out, nblk_el);
+        } else {
+          throw ClrsdpError{CLRSDP_E_ARG, "apply_operator: LIN mode must be CLRSDP_LIN_COPY, _SUB or _DIAG"};
+        }
+        *route = 0;
+        break;
+      }
+      default:
+        throw ClrsdpError{CLRSDP_E_ARG, "apply_operator: unknown op"};
     }
   }
 
@@ -4989,6 +5102,68 @@ void update_words(int device, const UpdateCall& c) {
   if (c.nblk) download_planes<T>(sc, c.step, 4);
 }
 
+struct ClSolveCall {
+  int64_t ncl;
+  const int64_t* D;
+  int64_t ny;
+  const double *Linv, *W, *rhs, *dy;
+  double *t, *slabs, *dx;
+};
+
+std::string cl_solve_check(const ClSolveCall& c) {
+  if (!c.D || !c.Linv || !c.W || !c.rhs || !c.dy || !c.t || !c.slabs || !c.dx) return "null argument";
+  if (c.ncl < 1 || c.ncl > 4096) return "ncl must be 1 .. 4096";
+  if (c.ny < 1) return "ny must be at least 1";
+  int64_t mx = 0;
+  for (int64_t q = 0; q < c.ncl; ++q) {
+    if (c.D[q] < 1 || c.D[q] > 256) return "every D must be 1 .. 256";
+    mx = std::max(mx, c.D[q]);
+  }
+  if (!cl_solve_ok(c.ncl, (int)cdiv(mx, 64), (int)mx, c.ny))
+    return "ny too large for the slab sum behind the cluster solve";
+  return "";
+}
+
+void cl_solve_run(int device, const ClSolveCall& c) {
+  DeviceGuard dg(device);
+  DevBuf mem;
+  int64_t nS = 0, nW = 0, nX = 0, mx = 0;
+  for (int64_t q = 0; q < c.ncl; ++q) {
+    nS += c.D[q] * c.D[q];
+    nW += c.D[q] * c.ny;
+    nX += c.D[q];
+    mx = std::max(mx, c.D[q]);
+  }
+  const int nrb = (int)cdiv(mx, 64);
+  const int64_t nslab = c.ncl * nrb * c.ny;
+  const double* L = upload_planes<double>(mem, c.Linv, nS);
+  const double* W = upload_planes<double>(mem, c.W, nW);
+  const double* rhs = upload_planes<double>(mem, c.rhs, nX);
+  const double* dy = upload_planes<double>(mem, c.dy, c.ny);
+  double* t = upload_planes<double>(mem, c.t, nX);
+  double* slabs = upload_planes<double>(mem, c.slabs, nslab);
+  double* dx = upload_planes<double>(mem, c.dx, nX);
+  std::vector<ClSolveDesc> h((size_t)c.ncl);
+  int64_t so = 0, wo = 0, xo = 0;
+  for (int64_t q = 0; q < c.ncl; ++q) {
+    const int64_t D = c.D[q];
+    ClSolveDesc cs{};
+    cs.L = L + so; cs.W = W + wo; cs.rhs = rhs + xo; cs.t = t + xo; cs.dx = dx + xo; cs.D = (int)D;
+    h[(size_t)q] = cs;
+    so += D * D; wo += D * c.ny; xo += D;
+  }
+  ClSolveDesc* ds = mem.alloc<ClSolveDesc>((size_t)c.ncl);
+  HIPCHK(hipMemcpy(ds, h.data(), h.size() * sizeof(ClSolveDesc), hipMemcpyHostToDevice));
+  StreamOwner so_;
+  launch_cl_solve_t(so_.s, ds, (int)c.ncl, nrb, (int)c.ny, slabs);
+  launch_cl_solve_dx(so_.s, ds, (int)c.ncl, nrb, (int)c.ny, dy);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(so_.s));
+  download_planes<double>(t, c.t, nX);
+  download_planes<double>(slabs, c.slabs, nslab);
+  download_planes<double>(dx, c.dx, nX);
+}
+
 }  // namespace
 
 struct clrsdp_handle {
@@ -5394,6 +5569,30 @@ int32_t clrsdp_update_state(int32_t device, int32_t words, int64_t nel, double* 
   const std::string bad = update_check(words, u);
   if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
   WORDS_CALL(update_words, device, u)
+}
+
+int32_t clrsdp_apply_operator(clrsdp_handle* h, int32_t op, const clrsdp_operands* a,
+                              int32_t* route) {
+  if (!h || !a || !route) { g_last_error = "null argument"; return CLRSDP_E_ARG; }
+  GUARD(h, { h->impl->apply_operator(op, a, route); return CLRSDP_OK; })
+}
+
+int32_t clrsdp_cl_solve(int32_t device, int64_t ncl, const int64_t* D, int64_t ny,
+                        const double* Linv, const double* W, const double* rhs, const double* dy,
+                        double* t, double* slabs, double* dx) {
+  const ClSolveCall c{ncl, D, ny, Linv, W, rhs, dy, t, slabs, dx};
+  const std::string bad = cl_solve_check(c);
+  if (!bad.empty()) { g_last_error = bad; return CLRSDP_E_ARG; }
+  try {
+    cl_solve_run(device, c);
+    return CLRSDP_OK;
+  } catch (const ClrsdpError& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return CLRSDP_E_HIP;
+  }
 }
 
 int32_t clrsdp_set_timing(clrsdp_handle* h, int32_t on) {

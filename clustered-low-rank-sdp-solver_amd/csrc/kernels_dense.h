@@ -4158,5 +4158,23 @@ __global__ __launch_bounds__(256) void cl_solve_dx(const ClSolveDesc* __restrict
   if ((lane & 3) == 0 && j < D) d.dx[j] = accx;
 }
 
+// The two launches and what they may be given, for the loop body (direction_solves) and the
+// stand-alone entry (clrsdp_cl_solve) alike: ncl clusters of at most 256 rows, nrb = cdiv(max D,
+// 64) <= 4 row blocks each, and a slab_qsolve behind them that re-forms r in every workgroup
+// (its read count and LDS bound)
+inline bool cl_solve_ok(long long ncl, int nrb, int max_D, long long ny) {
+  return ncl > 0 && ny > 0 && max_D >= 1 && max_D <= 256 && nrb >= 1 && nrb <= 4 &&
+         ((ny + 63) / 64) * (ncl * nrb) * ny <= (1LL << 20) &&
+         ((size_t)ny + 256) * sizeof(double) <= 64 * 1024;
+}
+inline void launch_cl_solve_t(hipStream_t s, const ClSolveDesc* ds, int ncl, int nrb, int ny,
+                              double* slabs) {
+  cl_solve_t<<<(unsigned)(ncl * nrb), 256, 0, s>>>(ds, nrb, ny, slabs);
+}
+inline void launch_cl_solve_dx(hipStream_t s, const ClSolveDesc* ds, int ncl, int nrb, int ny,
+                               const double* dy) {
+  cl_solve_dx<<<(unsigned)(ncl * nrb), 256, 0, s>>>(ds, nrb, ny, dy);
+}
+
 
 }  // namespace clrsdp

@@ -188,6 +188,50 @@ class DeviceSolver:
     def scalar(self, name: str, exact=False):
         return self.buffer(_lib.BUF_SCALARS, exact)[_lib.SC[name]]
 
+    def apply_operator(self, op: str, blocks=None, blocks2=None, tuples=None, scalar=None,
+                       mult: float = 1.0, mode: int = 0, only_m: bool = False, out=None):
+        """One of the handle's low-rank operators or block kernels on raw limbs
+        (clrsdp_apply_operator).  ``op``: "rhs" (blocks = Z, tuples = d -> -d - Tr(A_* Z)),
+        "weighted" (tuples = a, blocks = the base -> base + sum a_i A_i), "sym" (``mode`` 0, 1, 2,
+        ``only_m``) or "lin" (``mode`` LIN_COPY, LIN_SUB with ``blocks2``, LIN_DIAG with ``scalar``
+        (words limbs) and ``mult``).  Blocks are raw limbs of shape (words, n_blk) in the flat
+        local layout of ``buffer``, tuples (words, n_x); ``out`` pre-fills the output (default:
+        the payload).  Returns (raw limbs of the result, route).  The handle's work buffers are
+        unspecified afterwards: call set_state before a loop body."""
+        ops = {"rhs": _lib.APPLY_RHS, "weighted": _lib.APPLY_WEIGHTED, "sym": _lib.APPLY_SYM,
+               "lin": _lib.APPLY_LIN}
+        if op not in ops:
+            raise ValueError("op: " + ", ".join(ops))
+        if len(self.owned) != self.bi.J:
+            raise ValueError("apply_operator: a handle that owns every cluster (the local layout "
+                             "is then the global one)")
+        w = self.w
+        a = _lib.Operands()
+        keep = []
+
+        def limbs_of(v, n, what):
+            if v is None:
+                return None
+            arr = _limbs2(v, w, what, n)
+            keep.append(arr)
+            return _ptr(arr)
+
+        a.blocks = limbs_of(blocks, self.n_blk, "blocks")
+        a.blocks2 = limbs_of(blocks2, self.n_blk, "blocks2")
+        a.tuples = limbs_of(tuples, self.n_x, "tuples")
+        a.scalar = limbs_of(None if scalar is None else np.asarray(scalar, dtype=np.float64).reshape(w, 1),
+                            1, "scalar")
+        a.mult, a.mode, a.only_m = float(mult), int(mode), 1 if only_m else 0
+        nout = self.n_x if op == "rhs" else self.n_blk
+        res = _payload((w, nout)).copy() if out is None else _limbs2(out, w, "out", nout).copy()
+        if op == "rhs":
+            a.tuples_out = _ptr(res)
+        else:
+            a.blocks_out = _ptr(res)
+        route = C.c_int32(-1)
+        self.check(self.L.clrsdp_apply_operator(self.h, ops[op], C.byref(a), C.byref(route)))
+        return res, int(route.value)
+
     # ------------------------------------------------------------------ iteration
     def initial_residuals(self, prm: _lib.Params) -> _lib.IterStats:
         st = _lib.IterStats()
@@ -930,6 +974,29 @@ def update_state(X, dX, Y, dY, x, dx, c, y, dy, b, info, alpha=None, eig=None, g
     if step is not None:
         res["step"] = step
     return res
+
+
+def cl_solve(Linv, W, rhs, dy, guard=None, device: int = 0):
+    """The fp64 cluster solve in its two launches (clrsdp_cl_solve): per cluster c the D_c x D_c
+    ``Linv[c]`` (lower triangle read), the D_c x ny ``W[c]`` and ``rhs[c]``; ``dy`` of ny numbers.
+    t, the partial slabs and dx are pre-filled with ``guard`` (default: the payload).  Returns
+    (t, slabs, dx): t and dx as lists per cluster, slabs of shape (ncl, nrb, ny)."""
+    D = np.ascontiguousarray([np.asarray(l).shape[0] for l in Linv], dtype=np.int64)
+    ncl, ny = len(D), int(np.asarray(dy).size)
+    nrb = max(1, -(-int(D.max()) // 64)) if ncl else 1
+    cat = lambda ms: np.ascontiguousarray(np.concatenate(
+        [np.asarray(m, dtype=np.float64).reshape(-1, order="F") for m in ms])) if ncl else np.zeros(1)
+    Lf, Wf, rf = cat(Linv), cat(W), cat(rhs)
+    dyv = np.ascontiguousarray(dy, dtype=np.float64)
+    nx = int(D.sum())
+    fill = (lambda n: _payload((n,)).copy()) if guard is None else (lambda n: np.full(n, float(guard)))
+    t, slabs, dx = fill(max(nx, 1)), fill(max(ncl * nrb * ny, 1)), fill(max(nx, 1))
+    _lib.check(_lib.lib().clrsdp_cl_solve(device, ncl, D.ctypes.data_as(_lib.P_i64), ny, _ptr(Lf),
+                                          _ptr(Wf), _ptr(rf), _ptr(dyv), _ptr(t), _ptr(slabs),
+                                          _ptr(dx)))
+    off = np.concatenate([[0], np.cumsum(D)])
+    split = lambda v: [v[off[c]:off[c + 1]].copy() for c in range(ncl)]
+    return split(t), slabs[:ncl * nrb * ny].reshape(ncl, nrb, ny), split(dx)
 
 
 def initial_point(bi: BlockInfo, omega_p, omega_d):

@@ -723,6 +723,67 @@ int32_t clrsdp_update_state(int32_t device, int32_t words, int64_t nel, double* 
                             const double* eigX, const double* eigY, const double* gamma,
                             int32_t pd_feas, double* part, double* step);
 
+/* The low-rank operators and block kernels of a handle on operands the caller gives: the
+ * operands are copied into the handle's own work buffers as raw limbs (planes of the LOCAL
+ * layout of clrsdp_get_buffer: nblk numbers for blocks, nx for tuples; bit copies), the solver's
+ * own methods run with the descriptors and plans that build_plans made for this handle, and the
+ * result is copied back.  No factorisation and no positive-definite state is needed.  An output
+ * buffer is copied to the device first, so what the launches do not write comes back unchanged.
+ * Afterwards the handle's work buffers (residuals, directions, scratch) are unspecified: call
+ * clrsdp_set_state again before a loop body.  *route tells which kernels ran.
+ *   CLRSDP_APPLY_RHS       blocks = Z (taken as given: not symmetrised), tuples = d ->
+ *                          tuples_out = -d - Tr(A_* Z): the U = Z V product and direction_rhs_.
+ *                          route 0: the strip chain's TRACE form; 1: colsum_rhs;
+ *                          2: colsum_dot + tuple_aggregate.
+ *   CLRSDP_APPLY_WEIGHTED  tuples = a, blocks = the base -> blocks_out = base + sum_i a_i A_i as
+ *                          weighted_A(dx, p_wA_dX, dX, 1.0) forms dX = P + sum_i dx_i A_i (blocks
+ *                          with m > 1: of the base's upper block triangle, mirrored).
+ *                          route 0: the fused scaled GEMM; 1: scale_cols + GEMM (+ the mirror).
+ *   CLRSDP_APPLY_SYM       blocks -> blocks_out = sym(.) with mode 0 ((Z + Z^T)/2), 1 (the upper
+ *                          triangle mirrored), 2 (Z^T); only_m != 0: the blocks with m > 1 only.
+ *                          Modes 0 and 1 run in place, mode 2 out of place.
+ *                          route 0: blk_sym_tiles; 1: blk_sym2.
+ *   CLRSDP_APPLY_LIN       mode CLRSDP_LIN_COPY: blocks_out = blocks; CLRSDP_LIN_SUB: blocks_out =
+ *                          blocks - blocks2, in place as P - C; CLRSDP_LIN_DIAG: blocks_out =
+ *                          blocks + (*scalar) mult I with scalar (`words` limbs) read from a
+ *                          device word (diag_add alone).  route 0.
+ * CLRSDP_E_ARG: a NULL handle, operand struct, route or required buffer, an unknown op or mode.
+ * CLRSDP_E_STATE: constraints not uploaded, or loop bodies in flight. */
+#define CLRSDP_APPLY_RHS 0
+#define CLRSDP_APPLY_WEIGHTED 1
+#define CLRSDP_APPLY_SYM 2
+#define CLRSDP_APPLY_LIN 3
+#define CLRSDP_LIN_COPY 0
+#define CLRSDP_LIN_SUB 1
+#define CLRSDP_LIN_DIAG 2
+typedef struct {
+  const double* blocks;
+  const double* blocks2;
+  const double* tuples;
+  const double* scalar;
+  double mult;
+  int32_t mode, only_m;
+  double* blocks_out;
+  double* tuples_out;
+} clrsdp_operands;
+int32_t clrsdp_apply_operator(clrsdp_handle* h, int32_t op, const clrsdp_operands* a,
+                              int32_t* route);
+
+/* The cluster part of the block solve at fp64 in its two launches, through the helpers the loop
+ * body calls under CLRSDP_CL_SOLVE=1: cl_solve_t (t_c = L_c^-1 rhs_c and, per 64-row block, its
+ * share of W_c^T t_c into slabs), then cl_solve_dx (dx_c = L_c^-T (t_c + W_c dy)); grid
+ * ncl x nrb, nrb = ceil(max D / 64).  Cluster c has D[c] rows: Linv holds its D x D matrix
+ * (column-major, pitch D; only the lower triangle is read), W its D x ny matrix, rhs, t and dx its
+ * D numbers, all concatenated in cluster order; dy holds ny numbers; slabs ncl nrb ny numbers
+ * (slab (c nrb + block), zeros for a block past D[c]).  t, slabs and dx are copied to the device
+ * before the launches and back after them.
+ * Refused with CLRSDP_E_ARG before any device work: a NULL buffer; ncl outside 1 .. 4096; a D
+ * outside 1 .. 256; ny < 1; ceil(ny / 64) ncl nrb ny > 2^20 or (ny + 256) doubles beyond 64 KiB
+ * (the bounds of the slab_qsolve that sums the slabs). */
+int32_t clrsdp_cl_solve(int32_t device, int64_t ncl, const int64_t* D, int64_t ny,
+                        const double* Linv, const double* W, const double* rhs, const double* dy,
+                        double* t, double* slabs, double* dx);
+
 #ifdef __cplusplus
 }
 #endif
