@@ -44,7 +44,7 @@ EXPORTS = ["clrsdp_version", "clrsdp_last_error", "clrsdp_create", "clrsdp_uploa
            "clrsdp_reduce", "clrsdp_slab_sum", "clrsdp_update_state", "clrsdp_schur_info",
            "clrsdp_eigmin_kernel", "clrsdp_handoff_state", "clrsdp_chol_spdinv",
            "clrsdp_spdinv_kernel", "clrsdp_eigmin_routes", "clrsdp_apply_operator",
-           "clrsdp_cl_solve"]
+           "clrsdp_cl_solve", "clrsdp_potrf_kernel"]
 # clrsdp_apply_operator ops and the modes of its LIN op (include/clrsdp.h)
 APPLY_RHS, APPLY_WEIGHTED, APPLY_SYM, APPLY_LIN = range(4)
 LIN_COPY, LIN_SUB, LIN_DIAG = range(3)
@@ -52,6 +52,8 @@ LIN_COPY, LIN_SUB, LIN_DIAG = range(3)
 EIG_K_SPLIT, EIG_K_MX, EIG_K_LDS2, EIG_K_LDS, EIG_K_BATCHED, EIG_K_BLK, EIG_K_MXBLK = range(7)
 EIG_K_NAMES = {0: "eigmin_split", 1: "eigmin_mx", 2: "eigmin_lds2", 3: "eigmin_lds",
                4: "eigmin_batched", 5: "eigblk chain", 6: "mxblk route"}
+# clrsdp_potrf_kernel codes (include/clrsdp.h)
+POTRF_K_BATCHED, POTRF_K_LA64, POTRF_K_LA128, POTRF_K_BLK, POTRF_K_BLK64 = range(5)
 # clrsdp_set_factorization flags (include/clrsdp.h)
 FACT_FALLBACK, FACT_LU_SQ, FACT_LU_X = 1, 2, 4
 COMM_ID_BYTES = 128
@@ -184,7 +186,8 @@ def lib():
     L.clrsdp_eigmin_kernel.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]
     L.clrsdp_getrf.argtypes = [C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32, P_i32]
     L.clrsdp_potrf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_f64, P_i32]
-    L.clrsdp_chol_spdinv.argtypes = [C.c_int32, C.c_int64, P_i64, P_i64, P_i32, P_f64, P_f64, P_f64,
+    L.clrsdp_potrf_kernel.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int32)]
+    L.clrsdp_chol_spdinv.argtypes =[C.c_int32, C.c_int64, P_i64, P_i64, P_i32, P_f64, P_f64, P_f64,
                                      P_i32]
     L.clrsdp_spdinv_kernel.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
     L.clrsdp_trsm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P_i64, P_i64,

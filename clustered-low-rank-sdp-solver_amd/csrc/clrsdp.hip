@@ -152,9 +152,11 @@ inline void lds_attr_once(std::atomic<unsigned long long>& seen, const void* fn,
 // launch plans: descriptor arrays built once at creation, replayed every iteration
 // --------------------------------------------------------------------------------------------
 // a development switch is on when set to anything but a value starting with '0' (so that
-// NAME=0 switches it off again, for every switch alike)
-static inline bool env_on(const char* name) {
+// NAME=0 switches it off again, for every switch alike); *set, when given, tells whether it is
+// set at all
+static inline bool env_on(const char* name, bool* set = nullptr) {
   const char* e = std::getenv(name);
+  if (set) *set = e != nullptr;
   return e && e[0] != '0';
 }
 // a default-on switch is off only when set to a value starting with '0'
@@ -173,25 +175,71 @@ static inline long env_int(const char* name, long dflt, bool* exact = nullptr) {
   if (exact) *exact = end != e && *end == '\0';
   return v;
 }
-// (DESIGN.md §13 lists every switch read here, and the retired ones with their measurements)
 
-// chol_lookahead's switches (CLRSDP_LA_OPTS, kernels_dense.h).  Default 2: one Newton step for
-// the quad-double pivot reciprocal (~2^-208 relative; the second step was a third of the chain:
-// C5 879 -> 930 it/s, round 5 A/B); bit 0 (chain priority) measured nothing
-// Only bits 0 and 1 exist; any other value of CLRSDP_LA_OPTS (not a number, other bits) is
-// rejected with a message and the default kept.
-inline int la_opts() {
-  static const int o = [] {
-    bool exact = true;
-    const long v = env_int("CLRSDP_LA_OPTS", 2, &exact);
-    if (!exact || v < 0 || (v & ~3L)) {
+// The development switches as one value: a field per switch, at its default
+// until read() fills it from the environment.  That happens when a handle is created, when a
+// handle first builds its LU plans and at the top of each stand-alone call; the plans take what
+// they need from the value they are handed, so no captured loop body can change route behind it.
+struct Switches {
+  // three-state: -1 unset, 0 off, 1 on
+  int chain = -1, lu_blk = -1, potrf_blk = -1, schur_fused = -1, schur_fused_one = -1, trsm_blk = -1;
+  // off unless set (to anything not starting with '0')
+  bool chol256 = false, cl_solve = false, eig_blk = false, eig_mx_blk = false, eigmx_stats = false,
+       graph_mw = false, graph_rccl = false, no_graph = false, inject_capture_fail = false,
+       xy_overlap = false;
+  // on unless set to a value starting with '0'
+  bool chol_spdinv = true, eig_mx = true, lu_panel_lds = true, mw_pair_upper = true, ozaki = true,
+       qchol_main = true, seam_pub = true, schur_fused_d64 = true, schur_fused_y = true,
+       schur_grp2 = true;
+  long gemm_ts32_below = 192, trsm_kb = 128;
+  // chol_lookahead's option bits (kernels_dense.h).  Default 2: one Newton step for the
+  // quad-double pivot reciprocal (~2^-208 relative; the second step was a third of the chain:
+  // C5 879 -> 930 it/s, round 5 A/B); bit 0 (chain priority) measured nothing.  Only bits 0 and 1
+  // exist; any other value (not a number, other bits) is rejected with a message, once per
+  // process, and the default kept.
+  int la_opts = 2;
+  // the mxblk route of MatPlan::eigmin is off with CLRSDP_EIG_MX=0, as every refined-eigenpair route
+  bool mxblk() const { return eig_mx_blk && eig_mx; }
+
+  static Switches read() {
+    Switches s;
+    bool set = false;
+    s.chain = env_on("CLRSDP_CHAIN", &set) ? 1 : set ? 0 : -1;
+    s.chol256 = env_on("CLRSDP_CHOL256");
+    s.chol_spdinv = !env_off("CLRSDP_CHOL_SPDINV");
+    s.cl_solve = env_on("CLRSDP_CL_SOLVE");
+    s.eig_blk = env_on("CLRSDP_EIG_BLK");
+    s.eig_mx_blk = env_on("CLRSDP_EIG_MX_BLK");
+    s.eig_mx = !env_off("CLRSDP_EIG_MX");
+    s.eigmx_stats = env_on("CLRSDP_EIGMX_STATS");
+    s.gemm_ts32_below = env_int("CLRSDP_GEMM_TS32_BELOW", s.gemm_ts32_below);
+    s.graph_mw = env_on("CLRSDP_GRAPH_MW");
+    s.graph_rccl = env_on("CLRSDP_GRAPH_RCCL");
+    s.no_graph = env_on("CLRSDP_NO_GRAPH");
+    s.inject_capture_fail = env_on("CLRSDP_INJECT_CAPTURE_FAIL");
+    const long la = env_int("CLRSDP_LA_OPTS", s.la_opts, &set);  // (set: the value is a number)
+    static std::atomic<bool> told{false};
+    if (set && la >= 0 && !(la & ~3L)) s.la_opts = (int)la;
+    else if (!told.exchange(true))
       std::fprintf(stderr, "clrsdp: CLRSDP_LA_OPTS ignored (a number with bits 0 and 1 only); using 2\n");
-      return 2;
-    }
-    return (int)v;
-  }();
-  return o;
-}
+    s.lu_blk = env_on("CLRSDP_LU_BLK", &set) ? 1 : set ? 0 : -1;
+    s.lu_panel_lds = !env_off("CLRSDP_LU_PANEL_LDS");
+    s.mw_pair_upper = !env_off("CLRSDP_MW_PAIR_UPPER");
+    s.ozaki = !env_off("CLRSDP_OZAKI");
+    s.potrf_blk = env_on("CLRSDP_POTRF_BLK", &set) ? 1 : set ? 0 : -1;
+    s.qchol_main = !env_off("CLRSDP_QCHOL_MAIN");
+    s.seam_pub = !env_off("CLRSDP_SEAM_PUB");
+    s.schur_fused = env_on("CLRSDP_SCHUR_FUSED", &set) ? 1 : set ? 0 : -1;
+    s.schur_fused_one = env_on("CLRSDP_SCHUR_FUSED_ONE", &set) ? 1 : set ? 0 : -1;
+    s.schur_fused_d64 = !env_off("CLRSDP_SCHUR_FUSED_D64");
+    s.schur_fused_y = !env_off("CLRSDP_SCHUR_FUSED_Y");
+    s.schur_grp2 = !env_off("CLRSDP_SCHUR_GRP2");
+    s.trsm_blk = env_on("CLRSDP_TRSM_BLK", &set) ? 1 : set ? 0 : -1;
+    s.trsm_kb = env_int("CLRSDP_TRSM_KB", s.trsm_kb);
+    s.xy_overlap = env_on("CLRSDP_XY_OVERLAP");
+    return s;
+  }
+};
 // the largest block of the on-chip factorisation path (L^-1 and products instead of solves):
 // chol_inv_tiles (fp64) and chol_lookahead with the inverse (multi-word)
 template <class T> constexpr int reg_nmax() {
@@ -333,7 +381,7 @@ struct GemmPlan : PlanBase {
   // blocks: schur_assemble reads (min, max)); the launch lists those tiles only -- half the
   // VALU-bound multi-word work
   bool upper = false;
-  void finalize() {
+  void finalize(const Switches& sw) {
     if (h.empty()) return;
     if (sca && (ta || !tb || !std::is_same<T, double>::value))
       throw ClrsdpError{CLRSDP_E_ARG, "scaled-A GEMM: fp64 A B^T only"};
@@ -369,14 +417,14 @@ struct GemmPlan : PlanBase {
     }
     d = own(h);
     dt = own(t2d);
-    detect_uniform();
+    detect_uniform(sw.gemm_ts32_below);
   }
   // fp64 batches of one shape at constant operand strides take gemm_f64_uni (no descriptor
   // chain before the first operand load)
   bool uni = false;
   int uts = 64;  // gemm_f64_uni output tile (64 or 32)
   UniGemm ug{};
-  void detect_uniform() {
+  void detect_uniform(long ts32_below) {
     if constexpr (std::is_same<T, double>::value) {
       if (gemv || dyn || h.empty()) return;
       const GemmDesc<T>& g0 = h[0];
@@ -406,8 +454,6 @@ struct GemmPlan : PlanBase {
       // 32x32 tiles when the 64x64 tiles would leave most CUs idle (a small batch: one CU's
       // tile is then latency-bound, ~9.4 us for a 128^3 product against 6.5 us split over four
       // CUs, tools/micro/gemm_tiles.hip); CLRSDP_GEMM_TS32_BELOW sets the threshold (tiles)
-      // (read at every plan build, so a test can force either tile in one process)
-      const long ts32_below = env_int("CLRSDP_GEMM_TS32_BELOW", 192L);
       const long t64m = (long)cdiv(g0.M, 64), t64n = (long)cdiv(g0.N, 64);
       const long tiles64 = u.P * (sym ? t64m * (t64m + 1) / 2 : t64m * t64n);
       uts = tiles64 < ts32_below ? 32 : 64;
@@ -561,13 +607,6 @@ void GemmPlan<T>::launch_uni_impl(hipStream_t s, double alpha, double beta, cons
   }
 }
 
-// CLRSDP_TRSM_BLK: unset = trsm_batched wherever its panel fits in LDS and the blocked chain
-// across workgroups beyond; 1 the chain at every size trsm_batched would have served; 0
-// trsm_batched only (larger matrices: E_ARG)
-inline int trsm_blk_mode() {
-  return env_off("CLRSDP_TRSM_BLK") ? 0 : env_on("CLRSDP_TRSM_BLK") ? 1 : -1;
-}
-
 template <class T>
 struct TrsmPlan : PlanBase {
   // NC: right-hand sides per workgroup.  Multi-word solves with many right-hand sides
@@ -578,13 +617,14 @@ struct TrsmPlan : PlanBase {
   // kernel's static reciprocals.  Beyond LDS_MAX (fp64 n > 1199, dd 559, qd 239) the plan takes
   // the blocked chain: super-blocks of kb rows, each solved by trsm_batched on the sub-triangle
   // (per-step descriptors) and followed by trsm_blk_update on the rows not yet solved.
+  // CLRSDP_TRSM_BLK: unset that; 1 the chain at every size trsm_batched would have served; 0
+  // trsm_batched only (larger matrices: E_ARG)
   static constexpr size_t lu_lds_bytes(int n) {
     return sizeof(T) * ((size_t)NB * NB + (size_t)NB * NCW + (size_t)NB * n + NB);
   }
   static bool one_cu_fits(int n) { return lu_lds_bytes(n) <= LDS_MAX; }
   // the chain's super-block height (CLRSDP_TRSM_KB overrides; rounded down to a multiple of NB
   // that fits the panel): DESIGN.md §3 has the sweep
-  static constexpr int KB_DEFAULT = 128;
   bool blk = false;
   int kb = 0;
   struct Step { TrsmDesc<T>* d; int* dt; unsigned grid; };
@@ -620,7 +660,7 @@ struct TrsmPlan : PlanBase {
     h.push_back(t);
     nmax = std::max(nmax, n);
   }
-  void finalize() {
+  void finalize(const Switches& sw) {
     if (h.empty()) return;
     narrow = mode == 0 && !std::is_same<T, double>::value && rmax >= 32;
     vec = mode == 0 && !std::is_same<T, double>::value && nmax <= 128;
@@ -639,16 +679,13 @@ struct TrsmPlan : PlanBase {
         lds_attr_once(a64[3], (const void*)trsv_wave<T, false, NCV16>, (int)trsv_wave_lds<T>());
       }
     }
-    const int bm = trsm_blk_mode();
-    blk = !vec && (bm == 1 || (bm < 0 && !one_cu_fits(nmax)));
+    blk = !vec && (sw.trsm_blk == 1 || (sw.trsm_blk < 0 && !one_cu_fits(nmax)));
     if (!vec && !blk && !one_cu_fits(nmax))
       throw ClrsdpError{CLRSDP_E_ARG, "triangular solve: matrix too large for the on-chip panel of trsm_batched (CLRSDP_TRSM_BLK=0)"};
     if (blk) {
       int kmax = NB;
       while (one_cu_fits(kmax + NB)) kmax += NB;
-      long k = env_int("CLRSDP_TRSM_KB", KB_DEFAULT);
-      k = std::max<long>(NB, std::min<long>(k, kmax)) / NB * NB;
-      kb = (int)k;
+      kb = (int)(std::max<long>(NB, std::min<long>(sw.trsm_kb, kmax)) / NB * NB);
     }
     const int npan = blk ? std::min(kb, nmax) : nmax;  // rows of the largest on-chip solve
     if (lu_lds_bytes(npan) > 64 * 1024) {  // (outside any graph capture)
@@ -824,30 +861,33 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // 16-column panels: n = 127 x 16 blocks 230 -> 155 us (32-column panels: 201 us), while at
   // n <= 64 the one-CU chol_lookahead stays ahead (52 against 73 us; tools/micro/potrf_blk_bench)
   static constexpr int BLK_NB = 16;
-  // CLRSDP_POTRF_BLK is three-state (as CLRSDP_LU_BLK): unset = the above; 0 = no chain at any
-  // word type; explicitly on = the chain replaces potrf_batched at every word type -- fp64 at
-  // every n (potrf64_*, BLK64_NB-column panels, the trailing update on the fp64 matrix cores),
-  // quad-double above 64 (potrf_blk_* in chol_lookahead's LDL form) -- and with it goes
-  // potrf_batched's size bound.  The switch is read when the plan is finalised.
-  // fp64 panel width by measurement (tools/micro/potrf_blk_bench, 2 blocks, us, NB = 16 / 32 /
+  // the fp64 chain (potrf64_*, the trailing update on the fp64 matrix cores): panel width by
+  // measurement (tools/micro/potrf_blk_bench, 2 blocks, us, NB = 16 / 32 /
   // 64 against potrf_batched): n = 257 258 / 284 / 405 against 1277; n = 640 668 / 708 / 966
   // against 14180; n = 1262 1540 / 1600 / 2184 against 105903.  A panel costs its serial steps
   // (diag, the substitution) plus two launches, both growing with NB, while the update's 64 x 64
   // tiles are already spread over the chip at NB = 16.
   static constexpr int BLK64_NB = 16;
-  static bool chain_on() { return env_on("CLRSDP_POTRF_BLK"); }
+  // The kernel potrf() launches for a batch whose largest block is nmax (CLRSDP_POTRF_K_*,
+  // clrsdp.h), `potrf_blk` being the three-state CLRSDP_POTRF_BLK (as CLRSDP_LU_BLK): unset
+  // (-1) the chain for double-double above 64 only; 0 no chain at any word type; 1 the chain
+  // also wherever potrf_batched would run (fp64 at every n, quad-double above 64 in
+  // chol_lookahead's LDL form).  Only potrf_batched has a size bound (potrf_refusal).
+  static int potrf_dispatch(int nmax, int potrf_blk) {
+    if (std::is_same<T, double>::value) return potrf_blk == 1 ? CLRSDP_POTRF_K_BLK64 : CLRSDP_POTRF_K_BATCHED;
+    if (nmax <= 64) return CLRSDP_POTRF_K_LA64;
+    if (std::is_same<T, mw::dd>::value) {
+      if (potrf_blk != 0) return CLRSDP_POTRF_K_BLK;
+      return nmax <= LA_NMAX ? CLRSDP_POTRF_K_LA128 : CLRSDP_POTRF_K_BATCHED;
+    }
+    return potrf_blk == 1 ? CLRSDP_POTRF_K_BLK : CLRSDP_POTRF_K_BATCHED;
+  }
+  int route = -1;   // potrf()'s, stored by finalize(); -1: an EIG_ONLY plan, which potrf() refuses
+  int la_opts = 2;  // chol_lookahead's option bits, as finalize() was handed them
   BlkPotrfDesc<T>* bd = nullptr;
-  bool blk = false;
   // potrf_batched: 256 threads, double-double 1024 (see potrf())
   static constexpr int PB_NT = std::is_same<T, mw::dd>::value ? 1024 : 256;
   static size_t pb_lds_dyn(int n) { return sizeof(T) * ((size_t)NB * NB + (size_t)NB * n); }
-  // whether potrf() factors matrices up to n by potrf_batched (the rest: chol_lookahead or the
-  // potrf_blk_* chain, neither with a size bound)
-  static bool takes_potrf_batched(int n) {
-    if (std::is_same<T, double>::value) return !chain_on();
-    if (std::is_same<T, mw::dd>::value) return n > LA_NMAX && env_off("CLRSDP_POTRF_BLK");
-    return n > LA_NMAX && !chain_on();
-  }
   // static LDS of potrf_batched (rdg[], fail), from the code object (asked once per word type)
   static size_t pb_lds_static() {
     static const size_t bytes = [] {
@@ -864,14 +904,15 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   }
   // Past potrf_batched's panel the runtime would refuse the launch: the message of the refusal
   // (CLRSDP_E_ARG) for matrices up to nmax, empty where potrf() can run
-  static std::string potrf_refusal(int nmax) {
-    if (!takes_potrf_batched(nmax) || pb_lds_dyn(nmax) + pb_lds_static() <= LDS_MAX) return std::string();
+  static std::string potrf_refusal(int nmax, int potrf_blk) {
+    if (potrf_dispatch(nmax, potrf_blk) != CLRSDP_POTRF_K_BATCHED || pb_lds_dyn(nmax) + pb_lds_static() <= LDS_MAX)
+      return std::string();
     const char* w = std::is_same<T, double>::value ? "fp64" : std::is_same<T, mw::dd>::value ? "double-double" : "quad-double";
     return std::string("Cholesky factorization: a matrix of n = ") + std::to_string(nmax) +
            " is too large for the on-chip panel of potrf_batched (" + w + ": n <= " + std::to_string(pb_nmax()) + ")";
   }
-  static void check_potrf(int nmax) {
-    const std::string r = potrf_refusal(nmax);
+  static void check_potrf(int nmax, int potrf_blk) {
+    const std::string r = potrf_refusal(nmax, potrf_blk);
     if (!r.empty()) throw ClrsdpError{CLRSDP_E_ARG, r};
   }
   std::string refused;  // potrf() throws this (before any launch) instead of launching
@@ -883,41 +924,33 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   //                    (pivoted LU has no size bound);
   //   EIG_ONLY         only eigmin() runs: no such bound
   enum class Use { FACTOR, FACTOR_DEFERRED, EIG_ONLY };
-  void finalize(Use use = Use::FACTOR) {
+  void finalize(const Switches& sw, Use use = Use::FACTOR) {
     if (h.empty()) return;
+    la_opts = sw.la_opts;
     if (use != Use::EIG_ONLY) {
-      refused = potrf_refusal(nmax);
+      route = potrf_dispatch(nmax, sw.potrf_blk);
+      refused = potrf_refusal(nmax, sw.potrf_blk);
       if (!refused.empty() && use == Use::FACTOR) throw ClrsdpError{CLRSDP_E_ARG, refused};
     }
     d = own(h);
-    if constexpr (std::is_same<T, double>::value) {
-      blk = use != Use::EIG_ONLY && chain_on();
-      if (blk) {  // (substitution against L_kk: no L_kk^-1 scratch)
-        std::vector<BlkPotrfDesc<T>> b(h.size());
-        for (size_t q = 0; q < h.size(); ++q) b[q] = BlkPotrfDesc<T>{h[q].A, nullptr, h[q].n, h[q].lda};
-        bd = own(b);
-      }
-    } else {
-      if (std::is_same<T, mw::dd>::value) blk = nmax > 64 && !env_off("CLRSDP_POTRF_BLK");
-      else blk = nmax > LA_NMAX && chain_on();
-      if (blk) {
-        T* li = own(std::vector<T>(h.size() * BLK_NB * BLK_NB, T(0.0)));
-        std::vector<BlkPotrfDesc<T>> b(h.size());
-        for (size_t q = 0; q < h.size(); ++q)
-          b[q] = BlkPotrfDesc<T>{h[q].A, li + q * BLK_NB * BLK_NB, h[q].n, h[q].lda};
-        bd = own(b);
-      }
+    if (route == CLRSDP_POTRF_K_BLK64 || route == CLRSDP_POTRF_K_BLK) {
+      // the L_kk^-1 scratch of potrf_blk_* (potrf64_* substitutes against L_kk: none)
+      T* li = route == CLRSDP_POTRF_K_BLK ? own(std::vector<T>(h.size() * BLK_NB * BLK_NB, T(0.0))) : nullptr;
+      std::vector<BlkPotrfDesc<T>> b(h.size());
+      for (size_t q = 0; q < h.size(); ++q)
+        b[q] = BlkPotrfDesc<T>{h[q].A, li ? li + q * BLK_NB * BLK_NB : nullptr, h[q].n, h[q].lda};
+      bd = own(b);
     }
     if (!std::is_same<T, double>::value) redo = own(std::vector<int>(h.size(), 1));
-    eig_blk = use == Use::EIG_ONLY && env_on("CLRSDP_EIG_BLK");
-    eig_mxblk = use == Use::EIG_ONLY && mxblk_on();
-    const int ek = eig_dispatch(nmax, eig_blk, eig_mxblk);
+    const bool eig_blk = use == Use::EIG_ONLY && sw.eig_blk;
+    eig_stats = sw.eigmx_stats;
+    const int ek = eig_k = eig_dispatch(nmax, eig_blk, use == Use::EIG_ONLY && sw.mxblk(), sw.eig_mx);
     // the flagged blocks of the mxblk route go to the route the switch replaced; where
     // eigmin_batched would ask for more LDS than a launch gets unasked (it then cannot run
     // today either), to the multi-word chain
     mx_fb_chain = ek == CLRSDP_EIG_K_MXBLK && (eig_blk || batched_lds(nmax) > 64 * 1024);
     if (ek == CLRSDP_EIG_K_BLK || mx_fb_chain) finalize_eig_chain();
-    if (ek == CLRSDP_EIG_K_MXBLK) finalize_mxblk();
+    if (ek == CLRSDP_EIG_K_MXBLK) finalize_mxblk(sw);
   }
   static size_t batched_lds(int n) { return sizeof(T) * (4 * (size_t)n + 256); }  // eigmin_batched
   bool mx_fb_chain = false;
@@ -926,14 +959,12 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // batch that eigmin() would give to eigmin_batched (or, with CLRSDP_EIG_BLK=1, to the
   // multi-word chain) first goes through the fp64 chain, the fp64 Cholesky chain and a few
   // refinement steps at the word's width; the blocks Temple's bound does not certify are
-  // flagged in `redo`, and the route the switch replaced then runs on those alone.  Read when
-  // the plan is finalised, where all of its scratch is allocated.  Opt-in: DESIGN.md §1.
-  static bool mxblk_on() { return env_on("CLRSDP_EIG_MX_BLK") && !env_off("CLRSDP_EIG_MX"); }
+  // flagged in `redo`, and the route the switch replaced then runs on those alone.  All of its
+  // scratch is allocated when the plan is finalised.  Opt-in: DESIGN.md §1.
   // the first size of the route per word type: the first of eigmin_batched's range (the route
   // was ahead of both older routes there)
   static constexpr int MXBLK_NMIN = std::is_same<T, mw::dd>::value ? 97 : 67;
   static constexpr int MXBLK_NMAX = 4096;  // the 2^-40 margin of lam2 covers n 2^-52 up to here
-  bool eig_mxblk = false;
   MxBlkDesc<T>* md = nullptr;
   EigBlkDesc<double>* ed64 = nullptr;
   BlkPotrfDesc<double>* bd64 = nullptr;
@@ -944,7 +975,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   // tools/micro/eig_mxblk_bench: three events recorded behind the fp64 chain with its Sturm
   // step, the factor, and the inverse iteration (null in the library: a capture records none)
   hipEvent_t* mx_phase_ev = nullptr;
-  void finalize_mxblk() {
+  void finalize_mxblk(const Switches& sw) {
     if constexpr (!std::is_same<T, double>::value) {
       constexpr int R = EIG_R;
       const size_t nm = h.size();
@@ -983,7 +1014,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       md = own(m);
       ed64 = own(e);
       bd64 = own(b);
-      mx_ts.finalize();
+      mx_ts.finalize(sw);
       // every instance that can ask for more than 64 KiB of dynamic LDS, outside any capture
       static std::atomic<unsigned long long> ac{0}, as{0};
       lds_attr_once(ac, (const void*)eigblk_col<double, EIG_R>, (int)LDS_MAX);
@@ -1034,25 +1065,25 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   }
   // ---- lambda_min of blocks past the LDS kernels across workgroups (eigblk_*, kernels_dense.h)
   // CLRSDP_EIG_BLK=1: a batch that eigmin() would give to the one-CU eigmin_batched goes to the
-  // chain instead -- one launch per column over strips of EIG_R rows, then eigblk_sturm.  Read
-  // when the plan is finalised (a captured body cannot change route).  Opt-in: the measurements
-  // and the crossover against eigmin_batched are in DESIGN.md §1.
+  // chain instead -- one launch per column over strips of EIG_R rows, then eigblk_sturm.
+  // Opt-in: the measurements and the crossover against eigmin_batched are in DESIGN.md §1.
   // EIG_R: one thread per row and one wave per strip, so the strip height only decides how
   // many waves share the rows (tools/micro/eig_blk_bench)
   static constexpr int EIG_R = 64;
-  bool eig_blk = false;
+  bool eig_stats = false;  // CLRSDP_EIGMX_STATS: eigmin_mx's diagnostics instance
+  int eig_k = -1;          // eigmin()'s kernel (eig_dispatch), stored by finalize()
   bool eig_tri = true;  // eigblk_sturm keeps the tridiagonal in LDS
   EigBlkDesc<T>* ed = nullptr;
   // the largest n whose v_k and w (eigblk_col's dynamic LDS) fit one CU
   static constexpr int eig_chain_nmax() { return (int)(LDS_MAX / (2 * sizeof(T))); }
   // The kernel eigmin() launches for a batch whose largest block is nmax (CLRSDP_EIG_K_*,
-  // clrsdp.h), `chain` being CLRSDP_EIG_BLK and `mxblk` CLRSDP_EIG_MX_BLK as the plan read them
-  static int eig_dispatch(int nmax, bool chain, bool mxblk = false) {
+  // clrsdp.h), `chain` being CLRSDP_EIG_BLK, `mxblk` CLRSDP_EIG_MX_BLK (off with CLRSDP_EIG_MX=0)
+  // and `mx` CLRSDP_EIG_MX as the plan was handed them
+  static int eig_dispatch(int nmax, bool chain, bool mxblk, bool mx) {
     if (std::is_same<T, double>::value && nmax <= 128) return CLRSDP_EIG_K_SPLIT;  // matrix in registers
     if (!std::is_same<T, double>::value) {
       // n <= 64: an fp64 eigenpair refined at the word's width (eigmin_mx; the blocks it cannot
       // certify go to eigmin_lds2 in a second, flagged launch) unless CLRSDP_EIG_MX=0
-      static const bool mx = !env_off("CLRSDP_EIG_MX");
       if (mx && nmax <= 64 && eigmx_lds_bytes<T>(nmax) + EIGMX_STATIC_LDS <= LDS_MAX &&
           eig2_lds_bytes<T>(nmax) <= LDS_MAX)
         return CLRSDP_EIG_K_MX;
@@ -1108,63 +1139,61 @@ struct MatPlan : PlanBase {  // potrf / eigmin
   void potrf(hipStream_t s, int* info) const {
     if (h.empty()) return;
     if (!refused.empty()) throw ClrsdpError{CLRSDP_E_ARG, refused};
-    if constexpr (std::is_same<T, double>::value) {
-      if (blk) {
-        constexpr int NB = BLK64_NB;
-        const unsigned nm = (unsigned)h.size();
-        potrf64_first<NB><<<nm, 256, 0, s>>>(bd, info);
-        for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
-          const int rows = nmax - k0 - NB, nch = cdiv(rows, 64);
-          potrf64_trsm<NB><<<dim3((unsigned)nch, nm), 64, 0, s>>>(bd, k0, info);
-          potrf64_update<NB><<<dim3(1u + (unsigned)(nch * (nch + 1) / 2), nm), 256, 0, s>>>(bd, k0, info);
+    const unsigned nm = (unsigned)h.size();
+    switch (route) {
+      case CLRSDP_POTRF_K_BLK64:
+        if constexpr (std::is_same<T, double>::value) {
+          constexpr int NB = BLK64_NB;
+          potrf64_first<NB><<<nm, 256, 0, s>>>(bd, info);
+          for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
+            const int rows = nmax - k0 - NB, nch = cdiv(rows, 64);
+            potrf64_trsm<NB><<<dim3((unsigned)nch, nm), 64, 0, s>>>(bd, k0, info);
+            potrf64_update<NB><<<dim3(1u + (unsigned)(nch * (nch + 1) / 2), nm), 256, 0, s>>>(bd, k0, info);
+          }
         }
-        HIPCHK(hipGetLastError());
-        return;
-      }
-    } else {
-      if (blk) {
-        // (quad-double: the diagonal step in the LDL form of its chol_lookahead instances)
-        constexpr bool LDL = std::is_same<T, mw::qd>::value;
-        constexpr int NB = BLK_NB, DT = NB / 16;
-        const unsigned nm = (unsigned)h.size();
-        potrf_blk_first<T, LDL, NB><<<nm, 256, 0, s>>>(bd, info, la_opts());
-        for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
-          const int rows = nmax - k0 - NB, ntr = cdiv(rows, 16);
-          int tiles = 0;  // lower 16-tiles of the trailing matrix outside the next diagonal block
-          for (int I = DT; I < ntr; ++I) tiles += I + 1;
-          potrf_blk_trsm<T, NB><<<dim3((unsigned)ntr, nm), 256, 0, s>>>(bd, k0);
-          potrf_blk_update<T, LDL, NB><<<dim3(1u + tiles, nm), 256, 0, s>>>(bd, k0, info, la_opts());
+        break;
+      case CLRSDP_POTRF_K_BLK:
+        if constexpr (!std::is_same<T, double>::value) {
+          // (quad-double: the diagonal step in the LDL form of its chol_lookahead instances)
+          constexpr bool LDL = std::is_same<T, mw::qd>::value;
+          constexpr int NB = BLK_NB, DT = NB / 16;
+          potrf_blk_first<T, LDL, NB><<<nm, 256, 0, s>>>(bd, info, la_opts);
+          for (int k0 = 0; k0 + NB < nmax; k0 += NB) {
+            const int rows = nmax - k0 - NB, ntr = cdiv(rows, 16);
+            int tiles = 0;  // lower 16-tiles of the trailing matrix outside the next diagonal block
+            for (int I = DT; I < ntr; ++I) tiles += I + 1;
+            potrf_blk_trsm<T, NB><<<dim3((unsigned)ntr, nm), 256, 0, s>>>(bd, k0);
+            potrf_blk_update<T, LDL, NB><<<dim3(1u + tiles, nm), 256, 0, s>>>(bd, k0, info, la_opts);
+          }
         }
-        HIPCHK(hipGetLastError());
-        return;
-      }
-    }
-    if constexpr (!std::is_same<T, double>::value) {
-      if (nmax <= LA_NMAX) {
+        break;
+      case CLRSDP_POTRF_K_LA64:
         // at n <= 64 the bulk waves on the chain's SIMD stay idle (SKIP0, round 6: qd n = 51
         // 138 -> 126 us, dd n = 64 63 -> 61 us); quad-double in the square-root-free LDL form
-        const unsigned nm = (unsigned)h.size();
-        if constexpr (std::is_same<T, mw::dd>::value) {
-          if (nmax > 64) chol_lookahead<T, false, false, 128><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-          else chol_lookahead<T, false, false, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-        } else {
-          chol_lookahead<T, false, true, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts());
-        }
-        HIPCHK(hipGetLastError());
-        return;
-      }
+        if constexpr (std::is_same<T, mw::dd>::value)
+          chol_lookahead<T, false, false, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts);
+        else if constexpr (std::is_same<T, mw::qd>::value)
+          chol_lookahead<T, false, true, 64, 15, true><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts);
+        break;
+      case CLRSDP_POTRF_K_LA128:
+        if constexpr (std::is_same<T, mw::dd>::value)
+          chol_lookahead<T, false, false, 128><<<nm, 1024, 0, s>>>(d, nullptr, d, info, la_opts);
+        break;
+      case CLRSDP_POTRF_K_BATCHED:
+        // double-double: 1024 threads, so the trailing update (VALU bound) has four waves per
+        // SIMD (C4 factor stage 806 -> 724 us); quad-double keeps 256 (its registers, 3 % slower
+        // at 1024)
+        potrf_batched<T, NB, PB_NT><<<nm, PB_NT, pb_lds_dyn(nmax), s>>>(d, info);
+        break;
+      default:
+        throw ClrsdpError{CLRSDP_E_STATE, "potrf on a plan finalised for eigmin only"};
     }
-    const size_t lds = sizeof(T) * ((size_t)NB * NB + (size_t)NB * nmax);
-    // double-double: 1024 threads, so the trailing update (VALU bound) has four waves per SIMD
-    // (C4 factor stage 806 -> 724 us); quad-double keeps 256 (its registers, 3 % slower at 1024)
-    constexpr int NT = std::is_same<T, mw::dd>::value ? 1024 : 256;
-    potrf_batched<T, NB, NT><<<(unsigned)h.size(), NT, lds, s>>>(d, info);
     HIPCHK(hipGetLastError());
   }
   void eigmin(hipStream_t s, T* out) const {
     if (h.empty()) return;
     const unsigned nm = (unsigned)h.size();
-    switch (eig_dispatch(nmax, eig_blk, eig_mxblk)) {
+    switch (eig_k) {
       case CLRSDP_EIG_K_SPLIT:
         if constexpr (std::is_same<T, double>::value) {
           // eigmin_split: one reflector chain wave + 8 bulk waves, the last 24 columns on the
@@ -1175,8 +1204,7 @@ struct MatPlan : PlanBase {  // potrf / eigmin
       case CLRSDP_EIG_K_MX:
         if constexpr (!std::is_same<T, double>::value) {
           static std::atomic<unsigned long long> attrm{0}, attr2r{0};
-          static const bool dbg = env_on("CLRSDP_EIGMX_STATS");
-          if (dbg) {  // (the diagnostics instance: per-block eta / lambda / Temple width)
+          if (eig_stats) {  // (the diagnostics instance: per-block eta / lambda / Temple width)
             static std::atomic<unsigned long long> attrd{0};
             lds_attr_once(attrd, (const void*)eigmin_mx<T, 1>, (int)(LDS_MAX - EIGMX_STATIC_LDS));
             eigmin_mx<T, 1><<<nm, 576, eigmx_lds_bytes<T>(nmax), s>>>(d, out, redo);
@@ -1224,12 +1252,6 @@ struct MatPlan : PlanBase {  // potrf / eigmin
 };
 
 
-// CLRSDP_LU_BLK: unset (-1) the blocked LU chain (getrf_blk_*) where getrf_batched's on-chip
-// panel does not fit; 1 the chain at every size; 0 getrf_batched only (larger matrices: E_ARG)
-inline int lu_blk_mode() {
-  return env_off("CLRSDP_LU_BLK") ? 0 : env_on("CLRSDP_LU_BLK") ? 1 : -1;
-}
-
 // pivoted LU in place (the approx_lu! / approx_inv! fallback): getrf_batched, one workgroup per
 // matrix, wherever its panel and U12 fit in LDS (fp64 n <= 624, dd 312, qd 156), and the blocked
 // chain across workgroups beyond (getrf_blk_panel / _swap / _update per 16-column panel, looped
@@ -1247,9 +1269,10 @@ struct LuPlan : PlanBase {
     nmax = std::max(nmax, n);
   }
   static bool one_cu_fits(int n) { return getrf_lds_bytes<T, NB>(n) <= LDS_DYN; }
-  // which kernel factors matrices up to n: the chain (true) or getrf_batched; E_ARG when neither
-  static bool takes_chain(int n) {
-    const int m = lu_blk_mode();
+  // which kernel factors matrices up to n: the chain (true) or getrf_batched; E_ARG when neither.
+  // `m` is CLRSDP_LU_BLK: unset (-1) the blocked LU chain (getrf_blk_*) where getrf_batched's
+  // on-chip panel does not fit; 1 the chain at every size; 0 getrf_batched only
+  static bool takes_chain(int n, int m) {
     if (m == 1 || (m < 0 && !one_cu_fits(n))) return true;
     if (!one_cu_fits(n))
       throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: matrix too large for the on-chip panel of getrf_batched (CLRSDP_LU_BLK=0)"};
@@ -1260,13 +1283,13 @@ struct LuPlan : PlanBase {
   bool panel_lds = true;  // CLRSDP_LU_PANEL_LDS=0: the chain's panel in global memory at every size
   int* pivs = nullptr;    // the chain's pivot rows of the current panel, NB per matrix
   // (outside any graph capture: the LDS attributes are set and the pivot scratch allocated here)
-  void finalize() {
+  void finalize(const Switches& sw) {
     if (h.empty()) return;
-    blk = takes_chain(nmax);
+    blk = takes_chain(nmax, sw.lu_blk);
     d = own(h);
     if (blk) {
       pivs = own(std::vector<int>(h.size() * NB, 0));
-      panel_lds = !env_off("CLRSDP_LU_PANEL_LDS");
+      panel_lds = sw.lu_panel_lds;
       static std::atomic<unsigned long long> attr{0};
       lds_attr_once(attr, (const void*)getrf_blk_panel<T, NB, 256>, (int)LDS_DYN);
       return;
@@ -1344,8 +1367,10 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b, or A_b^-1
     hg.resize(hin.size(), MatDesc<T>{nullptr, 0, 0});
     hg.back() = MatDesc<T>{G, hin.back().n, ldg};
   }
-  void finalize() {
+  int la_opts = 2;  // chol_lookahead's option bits, as finalize() was handed them
+  void finalize(const Switches& sw) {
     if (hin.empty()) return;
+    la_opts = sw.la_opts;
     din = own(hin);
     dout = own(hout);
     if (!hl.empty()) dl = own(hl);
@@ -1376,8 +1401,8 @@ struct CholInvPlan : PlanBase {  // A_b -> L_b^-1 (and optionally L_b, or A_b^-1
       // on 4 waves -- one per SIMD, the chain alone on its SIMD -- instead of 16 (C5's X/Y
       // blocks <= 18: 980 -> 1007 it/s, round 5); SKIP0 at 64 as potrf's
       constexpr bool LDL = std::is_same<T, mw::qd>::value;
-      if (nmax <= 32) chol_lookahead<T, true, LDL, 32, 3><<<nb, 256, 0, s>>>(din, dout, dl, info, la_opts());
-      else if (nmax <= 64) chol_lookahead<T, true, LDL, 64, 15, true><<<nb, 1024, 0, s>>>(din, dout, dl, info, la_opts());
+      if (nmax <= 32) chol_lookahead<T, true, LDL, 32, 3><<<nb, 256, 0, s>>>(din, dout, dl, info, la_opts);
+      else if (nmax <= 64) chol_lookahead<T, true, LDL, 64, 15, true><<<nb, 1024, 0, s>>>(din, dout, dl, info, la_opts);
       else throw ClrsdpError{CLRSDP_E_ARG, "on-chip multi-word factorisation with inverse: n <= 64 only"};
     }
     HIPCHK(hipGetLastError());
@@ -1499,6 +1524,9 @@ static const StateConvertFn state_convert_fn[3][3] = {
     {launch_state_convert<qd, double>, launch_state_convert<qd, dd>, launch_state_convert<qd, qd>}};
 
 struct HandleBase {
+  // the switches as they stood when the handle was created: its plans, the members a switch
+  // decides and every loop body captured later follow them (the LU plans: Solver::lu_sw)
+  const Switches sw = Switches::read();
   std::string err;
   int dev = 0;  // the handle's HIP device (every C-ABI call on the handle runs with it current)
   virtual StateView state_view() const = 0;
@@ -1558,7 +1586,7 @@ struct Solver final : HandleBase {
   // the largest fp64 S_j factorised (and inverted) by ONE chol_inv_tiles launch: 256 with
   // CLRSDP_CHOL256=1 (chol_inv_tiles<256>, 768 threads: no 2x2 blocking, no X21 / W1 side
   // products), else 128
-  const int s_single = (std::is_same<T, double>::value && env_on("CLRSDP_CHOL256")) ? 256 : 128;
+  const int s_single = (std::is_same<T, double>::value && sw.chol256) ? 256 : 128;
   bool s_lower = false;  // the last SCHUR enqueued assembled the lower triangle of S only
   int schur_full = -1;   // the `full` of the last SCHUR enqueued (-1: none yet), for schur_info
 
@@ -1980,9 +2008,8 @@ struct Solver final : HandleBase {
       reg_blk = nmax_b <= reg_nmax<T>();
       reg_S = nmax_S <= (std::is_same<T, double>::value ? 2 : 1) * reg_nmax<T>();
       reg_Q = n_y <= reg_nmax<T>();
-      const bool spd_sw = !env_off("CLRSDP_CHOL_SPDINV");
-      spd_xy = reg_blk && nb() && CholInvPlan<T>::spdinv_dispatch(nmax_b, false, spd_sw);
-      spd_q = reg_Q && CholInvPlan<T>::spdinv_dispatch((int)n_y, false, spd_sw);
+      spd_xy = reg_blk && nb() && CholInvPlan<T>::spdinv_dispatch(nmax_b, false, sw.chol_spdinv);
+      spd_q = reg_Q && CholInvPlan<T>::spdinv_dispatch((int)n_y, false, sw.chol_spdinv);
       // multi-word S_j / Q beyond the on-chip inverse: GEMV solves with L^-1 instead of the
       // serial multi-word vector solves (four 41-us trsv_wave chains per direction at C5), in the
       // split form: potrf on the critical path and L^-1 = L \ I by four-wave solves (S_j's beside
@@ -2006,7 +2033,7 @@ struct Solver final : HandleBase {
     p_s2x.ta = p_s2y.ta = true;
     // (multi-word, every block m = 1: only the upper tiles of the symmetric pairings; CLRSDP_MW_PAIR_UPPER=0
     // computes both triangles)
-    mw_pair_upper = !std::is_same<T, double>::value && !anyMgt1 && !env_off("CLRSDP_MW_PAIR_UPPER");
+    mw_pair_upper = !std::is_same<T, double>::value && !anyMgt1 && sw.mw_pair_upper;
     p_s2x.upper = p_s2y.upper = mw_pair_upper;
     p_Q.ta = true;
     p_wA_P.tb = p_wA_dX.tb = true;
@@ -2107,8 +2134,7 @@ struct Solver final : HandleBase {
       for (size_t q = 0; q < lb.size() && uni_blk; ++q)
         uni_blk = lb[q].n == lb[0].n && lb[q].off == lb[0].off + (int64_t)q * lb[0].n * lb[0].n;
       const int n0 = lb.empty() ? 0 : lb[0].n;
-      const bool chains = uni_blk && n0 <= 128 && reg_blk && !env_off("CLRSDP_CHAIN") &&
-                          (env_on("CLRSDP_CHAIN") || n0 > 64);
+      const bool chains = uni_blk && n0 <= 128 && reg_blk && sw.chain != 0 && (sw.chain == 1 || n0 > 64);
       if (chains) {
         const int nbk = (int)lb.size();
         c_Z.init(n0, nbk, 1, false, false);
@@ -2136,13 +2162,13 @@ struct Solver final : HandleBase {
           e_Xs.add(tB + b.off, b.n, b.n);
           e_Ys.add(tC + b.off, b.n, b.n);
         }
-        e_Xs.finalize(MatPlan<T>::Use::EIG_ONLY);
-        e_Ys.finalize(MatPlan<T>::Use::EIG_ONLY);
+        e_Xs.finalize(sw, MatPlan<T>::Use::EIG_ONLY);
+        e_Ys.finalize(sw, MatPlan<T>::Use::EIG_ONLY);
         // CLRSDP_XY_OVERLAP=1 (round 6): with at most 32 local blocks the
         // X step length (its congruence and eigen launch) runs on the side stream as soon as the
         // corrector's dX exists, beside dY and the Y step length.  Measured, not the default
         // (DESIGN.md §7).
-        xy_ov_ok = env_on("CLRSDP_XY_OVERLAP") && nb() <= 32;
+        xy_ov_ok = sw.xy_overlap && nb() <= 32;
       }
     }
     n_blk_m = (int)bdm.size();
@@ -2352,10 +2378,9 @@ struct Solver final : HandleBase {
       // launches ran 14.8 + 21.4 us against 13.4 + 11.8 for the four GEMVs, and slab_qsolve
       // summing four partial slabs per cluster 13.7 against 9.0 us: 1195-1232 against 1248-1270
       // it/s, A/B round 5 -- fewer workgroups with longer load chains lose to more, shorter ones)
-      const bool cl_env = env_on("CLRSDP_CL_SOLVE");  // (per handle: tests switch it)
       int max_D = 0;
       for (const ClSolveDesc& cs : h_cls) max_D = std::max(max_D, cs.D);
-      cls_on = cl_env && std::is_same<T, double>::value && reg_S && reg_Q &&
+      cls_on = sw.cl_solve &&std::is_same<T, double>::value && reg_S && reg_Q &&
                cl_solve_ok(nc(), cls_nrb, max_D, n_y);
       if (cls_on) d_cls = descs.own(h_cls);
     }
@@ -2372,13 +2397,13 @@ struct Solver final : HandleBase {
                            &q_t, &q_Wdy, &q_dx, &q_q1, &q_q2, &q_qinv, &q_qdy, &f_a, &f_b, &f_c, &f_d, &f_x1, &f_x2, &f_w, &f_w2,
                            &q_t2, &q_dx2, &q_qinv2,
                            &p_wA_Ps, &p_wA_dXs, &p_xir})
-      g->finalize();
-    for (CholInvPlan<T>* c : {&ci_XY, &ci_S, &ci_S22, &ci_Q}) c->finalize();
-    e_XY.finalize(MatPlan<T>::Use::EIG_ONLY);
+      g->finalize(sw);
+    for (CholInvPlan<T>* c : {&ci_XY, &ci_S, &ci_S22, &ci_Q}) c->finalize(sw);
+    e_XY.finalize(sw, MatPlan<T>::Use::EIG_ONLY);
     for (TrsmPlan<T>* t : {&t_Linv, &t_W, &t_t, &t_Q, &t_sX1, &t_sX2, &t_sY1, &t_sY2, &t_dx, &t_Sinv, &t_Qinv})
-      t->finalize();
-    for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q}) f->finalize(MatPlan<T>::Use::FACTOR_DEFERRED);
-    for (MatPlan<T>* f : {&e_X, &e_Y}) f->finalize(MatPlan<T>::Use::EIG_ONLY);
+      t->finalize(sw);
+    for (MatPlan<T>* f : {&f_X, &f_Y, &f_S, &f_Q}) f->finalize(sw, MatPlan<T>::Use::FACTOR_DEFERRED);
+    for (MatPlan<T>* f : {&e_X, &e_Y}) f->finalize(sw, MatPlan<T>::Use::EIG_ONLY);
   }
 
   // ---- double-double Schur products on the int8 matrix cores (Ozaki scheme, oz_split / oz_gemm in
@@ -2404,7 +2429,7 @@ struct Solver final : HandleBase {
     oz_kx = nullptr;
     oz_nkx = 0;
     if constexpr (std::is_same<T, mw::dd>::value) {
-      if (anyMgt1 || lb.empty() || env_off("CLRSDP_OZAKI")) return;
+      if (anyMgt1 || lb.empty() || !sw.ozaki) return;
       std::vector<OzSplitDesc> s1, s2;
       std::vector<OzGemmDesc> g1, g2;
       std::vector<TileRef> s1t, s2t, g1t, g2t;
@@ -2476,7 +2501,6 @@ struct Solver final : HandleBase {
     HIPCHK(hipGetLastError());
   }
 
-  bool schur_grp2 = !env_off("CLRSDP_SCHUR_GRP2");  // (per handle: tests switch it)
   bool any_grp2 = false;
   void build_fast_schur() {
     if constexpr (std::is_same<T, double>::value) {
@@ -2507,7 +2531,7 @@ struct Solver final : HandleBase {
         }
         // every sample of rank 2 (C2): the pairs kernel sums the 2 x 2 groups into S itself
         // (CLRSDP_SCHUR_GRP2=0: G and schur_gsum, for A/B)
-        grp2 = grp2 && schur_grp2;
+        grp2 = grp2 && sw.schur_grp2;
         for (int l = 0; l < Lc[j]; ++l) {
           const LBlk& b = lb[bi + l];
           if (b.K == 0) continue;
@@ -2541,7 +2565,7 @@ struct Solver final : HandleBase {
       // shards), and in its ONE form below half the CUs (small cluster counts; at delta <= 64, C2,
       // the D64 instance).  Otherwise the unfused pair, with more and smaller workgroups.
       // CLRSDP_SCHUR_FUSED=0 / 1 forces either.
-      schur_fused = !env_off("CLRSDP_SCHUR_FUSED") && !ptd.empty();
+      schur_fused = sw.schur_fused != 0 && !ptd.empty();
       int fwg = 0;
       for (const PairTileDesc& t : ptd) {
         schur_fused = schur_fused && t.del <= 128;
@@ -2551,15 +2575,15 @@ struct Solver final : HandleBase {
       // taken (8-cluster shard of C3: 1572-1601 -> 1607-1681 it/s against the unfused pair, three
       // A/B pairs; at C2's delta = 64 it lost 2 %: 24.9 against 22.6 us)
       // (CLRSDP_SCHUR_FUSED_ONE=0: never, =1: whenever the fused kernel runs)
-      fused_one = fwg < 128 && !env_off("CLRSDP_SCHUR_FUSED_ONE");
+      fused_one = fwg < 128 && sw.schur_fused_one != 0;
       // (round 6, late: with every delta <= 64 the D64 instance of the ONE form -- half the MFMAs
       // of the padded one -- replaces the unfused pair below half the CUs, C2;
       // CLRSDP_SCHUR_FUSED_D64=0 keeps the padded instance wherever the fused kernel runs)
-      fused_d64 = !env_off("CLRSDP_SCHUR_FUSED_D64");
+      fused_d64 = sw.schur_fused_d64;
       for (const PairTileDesc& t : ptd) fused_d64 = fused_d64 && t.del <= 64;
       for (const PairTileDesc& t : ptd) fused_one = fused_one && (t.del > 64 || fused_d64);
-      if (env_on("CLRSDP_SCHUR_FUSED_ONE")) fused_one = true;
-      if (!env_on("CLRSDP_SCHUR_FUSED") && !fused_one) {
+      if (sw.schur_fused_one == 1) fused_one = true;
+      if (sw.schur_fused != 1 && !fused_one) {
         for (const PairTileDesc& t : ptd) schur_fused = schur_fused && t.del > 64;
         schur_fused = schur_fused && fwg >= 128;
       }
@@ -2588,7 +2612,7 @@ struct Solver final : HandleBase {
           fpd.push_back(f);
           fnt.push_back(cdiv(b.K, 64));
         }
-        fused_y = !env_off("CLRSDP_SCHUR_FUSED_Y");
+        fused_y = sw.schur_fused_y;
         fused_one = fused_one && fused_y;  // (instantiated with V^T Y on chip only)
         fused_d64 = fused_d64 && fused_one;   // (instantiated in the ONE form only)
         std::vector<TileRef> ft2d = tile_major(fnt);
@@ -2647,15 +2671,21 @@ struct Solver final : HandleBase {
     for (const LBlk& b : lb) nmax = std::max(nmax, b.n);
     return nmax;
   }
+  // the switches as read when the LU plans are first built (lazily, after creation): whether the
+  // handle fits, the error text and every plan finalised there take this one value
+  Switches lu_sw;
   bool lu_fits() const {
     const int nmax = lu_nmax();
-    if (lu_blk_mode() == 0 && !LuPlan<T>::one_cu_fits(nmax)) return false;
-    return trsm_blk_mode() != 0 || TrsmPlan<T>::one_cu_fits(nmax);
+    if (lu_sw.lu_blk == 0 && !LuPlan<T>::one_cu_fits(nmax)) return false;
+    return lu_sw.trsm_blk != 0 || TrsmPlan<T>::one_cu_fits(nmax);
   }
-  void build_lu_plans() {
-    if (lu_built) return;
+  // false (E_ARG when `must`): a matrix beyond the panels CLRSDP_LU_BLK=0 / CLRSDP_TRSM_BLK=0 keep it to
+  bool build_lu_plans(bool must = true) {
+    if (lu_built) return true;
+    lu_sw = Switches::read();
     if (!lu_fits()) {
-      if (trsm_blk_mode() == 0 && !TrsmPlan<T>::one_cu_fits(lu_nmax()))
+      if (!must) return false;
+      if (lu_sw.trsm_blk == 0 && !TrsmPlan<T>::one_cu_fits(lu_nmax()))
         throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of the LU triangular solves (CLRSDP_TRSM_BLK=0)"};
       throw ClrsdpError{CLRSDP_E_ARG, "LU factorization: a matrix is too large for the on-chip panel of getrf_batched (CLRSDP_LU_BLK=0)"};
     }
@@ -2672,6 +2702,7 @@ struct Solver final : HandleBase {
       W2m = nullptr;
       throw;
     }
+    return true;
   }
   void build_lu_plans_() {
     int64_t np = nx + n_y;
@@ -2713,11 +2744,11 @@ struct Solver final : HandleBase {
     lq_slab.ta = lq_Wt.ta = true;
     for (TrsmPlan<T>* t : {&tl_W1, &tl_t, &tl_Q1, &tl_X1}) t->mode = 1;
     for (TrsmPlan<T>* t : {&tl_W2, &tl_dx, &tl_Q2, &tl_X2}) t->mode = 2;
-    for (LuPlan<T>* l : {&lu_S, &lu_Q, &lu_X}) l->finalize();
+    for (LuPlan<T>* l : {&lu_S, &lu_Q, &lu_X}) l->finalize(lu_sw);
     for (PermPlan<T>* q : {&pm_B, &pm_rhs, &pm_r, &pm_I}) q->finalize();
-    for (TrsmPlan<T>* t : {&tl_W1, &tl_W2, &tl_t, &tl_dx, &tl_Q1, &tl_Q2, &tl_X1, &tl_X2}) t->finalize();
-    lq_slab.finalize();
-    lq_Wt.finalize();
+    for (TrsmPlan<T>* t : {&tl_W1, &tl_W2, &tl_t, &tl_dx, &tl_Q1, &tl_Q2, &tl_X1, &tl_X2}) t->finalize(lu_sw);
+    lq_slab.finalize(lu_sw);
+    lq_Wt.finalize(lu_sw);
     lu_built = true;
   }
   void set_factorization(int flags) override {
@@ -2983,10 +3014,9 @@ struct Solver final : HandleBase {
   // timing, the LU-fallback plans, a handle without graph replay) keeps stat_fetch().  A body
   // whose capture failed and that was enqueued eagerly instead publishes like the replayed one.
   char* stat_host_dev = nullptr;  // the mirror's device address
-  bool seam_pub = !env_off("CLRSDP_SEAM_PUB");
   bool pub_body = false;          // the body being enqueued publishes (read by scalars(.., 3))
   bool publish_ok(int pd_feas) const {
-    return seam_pub && std::is_same<T, double>::value && world == 1 && pd_feas >= 0 &&
+    return sw.seam_pub && std::is_same<T, double>::value && world == 1 && pd_feas >= 0 &&
            graph_ok() && !lu_sq() && !lu_x();
   }
   unsigned long long pub_seq_now() const {
@@ -3473,7 +3503,6 @@ struct Solver final : HandleBase {
   // t_j = L_j^-1 rhs_j and the slabs W_j^T t_j: the part of the batched solve that needs no Q^-1
   // (it waits for X21 / L_j^-1 where a side stream produced them).  body.head_ahead: the loop body
   // has run it on the side stream already, beside chol(Q)
-  bool qchol_main = !env_off("CLRSDP_QCHOL_MAIN");
   void solve_head() {
     h_x21.join(stream);
     h_sinv.join(stream);
@@ -3748,8 +3777,7 @@ struct Solver final : HandleBase {
     else if (rc == CLRSDP_E_NOT_PD_X && !lu_x()) add = CLRSDP_FACT_LU_X;
     // beyond the LU solves' panel (or getrf_batched's with CLRSDP_LU_BLK=0): the reference's
     // error stands
-    if (!add || !lu_fits()) return false;
-    build_lu_plans();
+    if (!add || !build_lu_plans(false)) return false;
     fact_flags |= add;
     drop_graphs();
     ++fallbacks;
@@ -3853,7 +3881,7 @@ struct Solver final : HandleBase {
     // to run meanwhile goes to the side stream behind the right-hand side: p and the error folds,
     // the guarded copy of p, and the head of the predictor's solve (t = L^-1 rhs, the slabs
     // W^T t), none of which reads Q.  One join, just before the Q solve; no fork for chol(Q).
-    const bool q_main = qchol_main && std::is_same<T, double>::value && world == 1 && timing != 1 &&
+    const bool q_main = sw.qchol_main && std::is_same<T, double>::value && world == 1 && timing != 1 &&
                         nc() && !lu_sq() && !cls_on;
     {
       h_w.join(aux);
@@ -3918,11 +3946,11 @@ struct Solver final : HandleBase {
   // C4 (dd) 620-625 against 600-617 with the replayed graph (A/B, round 4); fp64 keeps the
   // replay (C3 equal, C2 2288-2315 against 2122-2288 eager); CLRSDP_GRAPH_MW=1 replays
   // multi-word bodies too
-  bool use_graph = !env_on("CLRSDP_NO_GRAPH") && (sizeof(T) == 8 || env_on("CLRSDP_GRAPH_MW"));
+  bool use_graph = !sw.no_graph && (sizeof(T) == 8 || sw.graph_mw);
   // multi-rank loop bodies with the native communicator are enqueued eagerly by default (the
   // pipelined host loop hides the enqueue); CLRSDP_GRAPH_RCCL=1 captures the all-gathers into
   // the replayed graph as well
-  bool graph_rccl = env_on("CLRSDP_GRAPH_RCCL");
+  bool graph_rccl = sw.graph_rccl;
   void set_graph(int on) override {
     if (inflight) throw ClrsdpError{CLRSDP_E_STATE, "set_graph with loop bodies in flight"};
     use_graph = on != 0;
@@ -3986,7 +4014,7 @@ struct Solver final : HandleBase {
   // CLRSDP_INJECT_CAPTURE_FAIL=1 (tests only, read per handle): the first capture of a loop body
   // throws half-way through its enqueue, after the side streams were forked and the pending
   // flags set, and the body takes the sharded path's eager fallback even at one rank
-  bool inject_capture_fail = env_on("CLRSDP_INJECT_CAPTURE_FAIL");
+  bool inject_capture_fail = sw.inject_capture_fail;
   bool capturing = false;
   // the per-body enqueue state a failed (partial) capture may have left set; an eager re-enqueue
   // must not wait on events recorded only inside the aborted capture
@@ -4415,6 +4443,7 @@ void download_planes(const T* d, double* planes, int64_t cnt) {
 template <class T>
 void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, double* ep,
                   int32_t* route = nullptr) {
+  const Switches sw = Switches::read();
   DeviceGuard dg(device);
   std::vector<int64_t> off(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) {
@@ -4426,7 +4455,7 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
   T* eig = mem.alloc<T>(nblk);
   MatPlan<T> eg;
   for (int64_t b = 0; b < nblk; ++b) eg.add(A + off[b], (int)n[b], (int)n[b]);
-  eg.finalize(MatPlan<T>::Use::EIG_ONLY);
+  eg.finalize(sw, MatPlan<T>::Use::EIG_ONLY);
   StreamOwner so;
   eg.eigmin(so.s, eig);
   HIPCHK(hipGetLastError());
@@ -4435,14 +4464,14 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
   if (!route) return;
   // per block: 0 certified by the refinement, 1 flagged and computed by the fallback launch;
   // -1 for a batch whose kernel has no certification step
-  const int ek = MatPlan<T>::eig_dispatch(eg.nmax, eg.eig_blk, eg.eig_mxblk);
+  const int ek = eg.eig_k;
   if ((ek != CLRSDP_EIG_K_MX && ek != CLRSDP_EIG_K_MXBLK) || !eg.redo) {
     for (int64_t b = 0; b < nblk; ++b) route[b] = -1;
     return;
   }
   static_assert(sizeof(int) == sizeof(int32_t), "the flags are 32-bit");
   HIPCHK(hipMemcpy(route, eg.redo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
-  if (ek == CLRSDP_EIG_K_MXBLK && env_on("CLRSDP_EIGMX_STATS")) {
+  if (ek == CLRSDP_EIG_K_MXBLK && sw.eigmx_stats) {
     std::vector<double> st((size_t)nblk * MXBLK_ST);
     HIPCHK(hipMemcpy(st.data(), eg.mx_st, st.size() * sizeof(double), hipMemcpyDeviceToHost));
     int flagged = 0, steps = 0;
@@ -4459,6 +4488,7 @@ void eigmin_words(int device, int64_t nblk, const int64_t* n, const double* Ap, 
 // (getrf_batched, or the blocked chain beyond its panel / with CLRSDP_LU_BLK=1): planes in and out
 template <class T>
 void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t* perm, int32_t* info) {
+  const Switches sw = Switches::read();
   std::vector<int64_t> off(nblk + 1, 0), poff(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) {
     off[b + 1] = off[b] + n[b] * n[b];
@@ -4472,7 +4502,7 @@ void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t
   int* dinfo = mem.alloc<int>(nblk);
   LuPlan<T> lu;
   for (int64_t b = 0; b < nblk; ++b) lu.add(A + off[b], dperm + poff[b], (int)n[b], (int)n[b]);
-  lu.finalize();
+  lu.finalize(sw);
   StreamOwner so;
   lu.launch(so.s, dinfo);
   HIPCHK(hipStreamSynchronize(so.s));
@@ -4488,12 +4518,13 @@ void getrf_words(int device, int64_t nblk, const int64_t* n, double* Ap, int32_t
 // (inverse = 1); planes in and out
 template <class T>
 void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double* Ap, int32_t* info) {
+  const Switches sw = Switches::read();
   std::vector<int64_t> off(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) off[b + 1] = off[b] + n[b] * n[b];
   DeviceGuard dg(device);
   // potrf_batched's size bound (E_ARG) before any buffer is allocated or copied; fac.finalize()
   // below makes the same comparison again, on the cached figure
-  if (!inverse) MatPlan<T>::check_potrf((int)*std::max_element(n, n + nblk));
+  if (!inverse) MatPlan<T>::check_potrf((int)*std::max_element(n, n + nblk), sw.potrf_blk);
   const int64_t tot = off[nblk];
   DevBuf mem;
   T* A = upload_planes<T>(mem, Ap, tot);
@@ -4505,8 +4536,8 @@ void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double
     if (inverse) ci.add(A + off[b], (int)n[b], (int)n[b], X + off[b], (int)n[b]);
     else fac.add(A + off[b], (int)n[b], (int)n[b]);
   }
-  fac.finalize();
-  ci.finalize();
+  fac.finalize(sw);
+  ci.finalize(sw);
   StreamOwner so;
   if (inverse) {
     HIPCHK(hipMemsetAsync(X, 0xFF, (size_t)tot * sizeof(T), so.s));
@@ -4526,6 +4557,7 @@ void potrf_words(int device, int inverse, int64_t nblk, const int64_t* n, double
 // unchanged
 static void chol_spdinv_f64(int device, int64_t nblk, const int64_t* n, const int64_t* ld, const int32_t* want,
                      const double* Ap, double* Linv, double* Ainv, int32_t* info) {
+  const Switches sw = Switches::read();
   std::vector<int64_t> off(nblk + 1, 0), ooff(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) {
     off[b + 1] = off[b] + n[b] * n[b];
@@ -4552,7 +4584,7 @@ static void chol_spdinv_f64(int device, int64_t nblk, const int64_t* n, const in
     }
   }
   if (!any) ci.want_inverse(nullptr, 0);  // (a descriptor list of nulls: the same instance)
-  ci.finalize();
+  ci.finalize(sw);
   StreamOwner so;
   ci.launch(so.s, dinfo, true);
   HIPCHK(hipGetLastError());
@@ -4569,6 +4601,7 @@ static void chol_spdinv_f64(int device, int64_t nblk, const int64_t* n, const in
 template <class T>
 void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n, const int64_t* nrhs,
                 const double* Ap, double* Bp) {
+  const Switches sw = Switches::read();
   std::vector<int64_t> off(nblk + 1, 0), boff(nblk + 1, 0);
   for (int64_t b = 0; b < nblk; ++b) {
     off[b + 1] = off[b] + n[b] * n[b];
@@ -4583,7 +4616,7 @@ void trsm_words(int device, int mode, int trans, int64_t nblk, const int64_t* n,
   tp.mode = mode;
   for (int64_t b = 0; b < nblk; ++b)
     tp.add(A + off[b], (int)n[b], B + boff[b], (int)n[b], (int)n[b], (int)nrhs[b]);
-  tp.finalize();
+  tp.finalize(sw);
   StreamOwner so;
   tp.launch(so.s, trans != 0);
   HIPCHK(hipStreamSynchronize(so.s));
@@ -4606,6 +4639,7 @@ struct GemmCall {
 // One GemmPlan<T> from the records, built as build_plans() builds the solver's, launched once
 template <class T>
 int gemm_words(int device, const GemmCall& c) {
+  const Switches sw = Switches::read();
   DeviceGuard dg(device);
   DevBuf mem;
   const T* A = upload_planes<T>(mem, c.A, c.na);
@@ -4647,7 +4681,7 @@ int gemm_words(int device, const GemmCall& c) {
       g.add(A + r.offa, (int)r.lda, B + r.offb, (int)r.ldb, ci, ldci, C + r.offc, (int)r.ldc, M, N, K);
     }
   }
-  g.finalize();
+  g.finalize(sw);
   StreamOwner so;
   g.launch(so.s, c.alpha, c.beta, c.form == CLRSDP_GEMM_MIXED ? nullptr : ds, c.dmult);
   HIPCHK(hipGetLastError());
@@ -4765,6 +4799,7 @@ int chain_run(int device, const ChainCall& c) {
 
 int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh, const double* dMh,
                     double gamma, double* alpha, double* min_eig, std::string& err) {
+  const Switches sw = Switches::read();
   DeviceGuard dg(device);
   std::vector<int64_t> off(nblk + 1, 0);
   int nmax = 0;
@@ -4806,8 +4841,8 @@ int step_length_f64(int device, int64_t nblk, const int64_t* n, const double* Mh
     }
     eg.add(t2 + o, nb, nb);
   }
-  ci.finalize(); g1.finalize(); g2.finalize(); fac.finalize(); eg.finalize(MatPlan<double>::Use::EIG_ONLY);
-  s1.finalize(); s2.finalize();
+  ci.finalize(sw); g1.finalize(sw); g2.finalize(sw); fac.finalize(sw); eg.finalize(sw, MatPlan<double>::Use::EIG_ONLY);
+  s1.finalize(sw); s2.finalize(sw);
   PlanBase bd_owner;
   BlkDesc* d_big = big.empty() ? nullptr : bd_owner.own(big);
   StreamOwner so;
@@ -5373,10 +5408,10 @@ int32_t clrsdp_step_length(int32_t device, int64_t nblocks, const int64_t* n, co
 
 int32_t clrsdp_eigmin_kernel(int32_t words, int64_t nmax, int32_t* kernel) {
   if (!kernel || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
-  const bool chain = env_on("CLRSDP_EIG_BLK"), mxblk = MatPlan<mw::dd>::mxblk_on();
-  if (words == 1) *kernel = MatPlan<double>::eig_dispatch((int)nmax, chain);
-  else if (words == 2) *kernel = MatPlan<mw::dd>::eig_dispatch((int)nmax, chain, mxblk);
-  else if (words == 4) *kernel = MatPlan<mw::qd>::eig_dispatch((int)nmax, chain, mxblk);
+  const Switches sw = Switches::read();
+  if (words == 1) *kernel = MatPlan<double>::eig_dispatch((int)nmax, sw.eig_blk, sw.mxblk(), sw.eig_mx);
+  else if (words == 2) *kernel = MatPlan<mw::dd>::eig_dispatch((int)nmax, sw.eig_blk, sw.mxblk(), sw.eig_mx);
+  else if (words == 4) *kernel = MatPlan<mw::qd>::eig_dispatch((int)nmax, sw.eig_blk, sw.mxblk(), sw.eig_mx);
   else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
   return CLRSDP_OK;
 }
@@ -5436,6 +5471,16 @@ int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nbl
   WORDS_CALL(potrf_words, device, inverse, nblocks, n, A, info)
 }
 
+int32_t clrsdp_potrf_kernel(int32_t words, int64_t nmax, int32_t* kernel) {
+  if (!kernel || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
+  const int potrf_blk = Switches::read().potrf_blk;
+  if (words == 1) *kernel = MatPlan<double>::potrf_dispatch((int)nmax, potrf_blk);
+  else if (words == 2) *kernel = MatPlan<mw::dd>::potrf_dispatch((int)nmax, potrf_blk);
+  else if (words == 4) *kernel = MatPlan<mw::qd>::potrf_dispatch((int)nmax, potrf_blk);
+  else { g_last_error = "words must be 1, 2 or 4"; return CLRSDP_E_ARG; }
+  return CLRSDP_OK;
+}
+
 int32_t clrsdp_chol_spdinv(int32_t device, int64_t nblocks, const int64_t* n, const int64_t* ld,
                            const int32_t* want, const double* A, double* Linv, double* Ainv,
                            int32_t* info) {
@@ -5459,7 +5504,7 @@ int32_t clrsdp_chol_spdinv(int32_t device, int64_t nblocks, const int64_t* n, co
 
 int32_t clrsdp_spdinv_kernel(int32_t words, int64_t nmax, int32_t lu, int32_t* fused) {
   if (!fused || nmax <= 0 || nmax > 4096) { g_last_error = "null argument or nmax outside 1 .. 4096"; return CLRSDP_E_ARG; }
-  const bool sw = !env_off("CLRSDP_CHOL_SPDINV");
+  const bool sw = Switches::read().chol_spdinv;
   if (words == 1) *fused = CholInvPlan<double>::spdinv_dispatch((int)nmax, lu != 0, sw);
   else if (words == 2) *fused = CholInvPlan<mw::dd>::spdinv_dispatch((int)nmax, lu != 0, sw);
   else if (words == 4) *fused = CholInvPlan<mw::qd>::spdinv_dispatch((int)nmax, lu != 0, sw);
@@ -5633,9 +5678,9 @@ int32_t clrsdp_get_factorization(const clrsdp_handle* h, int32_t* flags) {
 
 int32_t clrsdp_destroy(clrsdp_handle* h) {
   if (!h) return CLRSDP_OK;
-  // CLRSDP_EIGMX_STATS=1: how many blocks eigmin_mx and the mxblk route handed to the multi-word
-  // path so far (all handles of the process; diagnostics only)
-  if (env_on("CLRSDP_EIGMX_STATS")) {
+  // CLRSDP_EIGMX_STATS=1 when the handle was created: how many blocks eigmin_mx and the mxblk
+  // route handed to the multi-word path so far (all handles of the process; diagnostics only)
+  if (h->impl && h->impl->sw.eigmx_stats) {
     unsigned int fb = 0, ms = 0;
     if (hipMemcpyFromSymbol(&fb, HIP_SYMBOL(g_eigmx_fallbacks), sizeof(fb)) == hipSuccess &&
         hipMemcpyFromSymbol(&ms, HIP_SYMBOL(g_mxblk_steps), sizeof(ms)) == hipSuccess)

@@ -426,6 +426,16 @@ def eigmin_kernel(nmax: int, precision_words: int = 1) -> int:
     return k.value
 
 
+def potrf_kernel(nmax: int, precision_words: int = 1) -> int:
+    """Which kernel ``potrf`` without the inverse (and the FACTOR stage's Cholesky launches) takes
+    for a batch whose largest block is ``nmax``, under the current environment
+    (``CLRSDP_POTRF_BLK``): one of ``_lib.POTRF_K_*`` (clrsdp_potrf_kernel; a host-only query, no
+    device and no launch).  It answers the route, not potrf_batched's size refusal."""
+    k = C.c_int32(-1)
+    _lib.check(_lib.lib().clrsdp_potrf_kernel(int(precision_words), int(nmax), C.byref(k)))
+    return k.value
+
+
 def spdinv_kernel(nmax: int, precision_words: int = 1, lu: bool = False) -> bool:
     """Whether the XINV stage / chol(Q) of a batch whose largest block is ``nmax`` form the
     inverse inside the factorisation's launch (True) or by a GEMM behind it, under the current

@@ -481,6 +481,18 @@ int32_t clrsdp_getrf(int32_t device, int32_t words, int64_t nblocks, const int64
 int32_t clrsdp_potrf(int32_t device, int32_t words, int32_t inverse, int64_t nblocks,
                      const int64_t* n, double* A, int32_t* info);
 
+/* Which kernel clrsdp_potrf with inverse = 0 (and the FACTOR stage's Cholesky launches) takes for
+ * a batch at `words` whose largest block is nmax (1 .. 4096), under the current environment
+ * (CLRSDP_POTRF_BLK).  A host-only query: no device is touched and nothing is launched.  It
+ * answers the route, not potrf_batched's size refusal, which needs the kernel's static LDS from
+ * the code object and so a device. */
+#define CLRSDP_POTRF_K_BATCHED 0  /* potrf_batched (one workgroup per block, 16-column panels)    */
+#define CLRSDP_POTRF_K_LA64 1     /* chol_lookahead<.., 64, 15, true>; the LDL form at quad-double */
+#define CLRSDP_POTRF_K_LA128 2    /* chol_lookahead<.., 128> (double-double only)                 */
+#define CLRSDP_POTRF_K_BLK 3      /* potrf_blk_* chain across workgroups (multi-word)             */
+#define CLRSDP_POTRF_K_BLK64 4    /* potrf64_* chain across workgroups (fp64)                     */
+int32_t clrsdp_potrf_kernel(int32_t words, int64_t nmax, int32_t* kernel);
+
 /* L_b^-1 and, for the blocks that ask, A_b^-1 = L_b^-T L_b^-1 of fp64 symmetric positive definite
  * blocks in ONE launch of the form of chol_inv_tiles that keeps the tiles of A^-1 in its
  * accumulators (the XINV stage's launch, and chol(Q)'s).  A: nblocks blocks of sizes n[]

@@ -4,19 +4,13 @@ has eigmin_batched for double-double and quad-double, from the first size of tha
 nowhere else; unset, 0 and CLRSDP_EIG_MX=0 give the table without it; CLRSDP_EIG_BLK=1 does not
 move it; fp64 never takes it.
 
-CLRSDP_EIG_MX is read once per process by the dispatch of n <= 64, so its case runs in a fresh
-interpreter: there the table with CLRSDP_EIG_MX_BLK=1 is the table with the switch unset."""
-import json
-import os
-import subprocess
-import sys
-
+Every query reads the environment afresh, CLRSDP_EIG_MX included: with CLRSDP_EIG_MX=0 the table
+with CLRSDP_EIG_MX_BLK=1 is the table with the switch unset."""
 import pytest
 
 import test_eig_dispatch_host as dh
 
 SPLIT, MX, LDS2, LDS, BATCHED, BLK, MXBLK = range(7)   # CLRSDP_EIG_K_* (include/clrsdp.h)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the first size the route takes, per word width (MatPlan<T>::MXBLK_NMIN): the first of
 # eigmin_batched's range
 NMIN = {2: 97, 4: 67}
@@ -83,31 +77,28 @@ def test_fp64_never_takes_it(pk, env):
         assert all(pk.eigmin_kernel(n, 1) != MXBLK for n in list(range(1, 300)) + [1024, 4096])
 
 
-_CHILD = """
-import json, sys
-sys.path.insert(0, {root!r})
-import _clrsdp_pkg
-pk = _clrsdp_pkg.load()
-keys = {keys!r}
-print(json.dumps([pk.eigmin_kernel(n, w) for w, n in keys]))
-"""
-
-
-def _child_table(extra):
-    keys = sorted(dh.TABLE)
-    e = {k: v for k, v in os.environ.items() if k not in ("CLRSDP_EIG_BLK", "CLRSDP_EIG_MX_BLK")}
-    e["CLRSDP_EIG_MX"] = "0"
-    e.update(extra)
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(root=ROOT, keys=keys)], env=e,
-                       capture_output=True, text=True, check=True)
-    return dict(zip(keys, json.loads(r.stdout.strip().splitlines()[-1])))
-
-
-def test_off_with_eig_mx_0():
+def test_off_with_eig_mx_0(pk, env):
     """CLRSDP_EIG_MX=0 switches every refined-eigenpair route off: the table with
     CLRSDP_EIG_MX_BLK=1 is the table without it (eigmin_lds2 in eigmin_mx's range, eigmin_batched
     in its own)."""
-    on, off = _child_table({"CLRSDP_EIG_MX_BLK": "1"}), _child_table({})
+    env.setenv("CLRSDP_EIG_MX", "0")
+    off = _table(pk)
+    env.setenv("CLRSDP_EIG_MX_BLK", "1")
+    on = _table(pk)
     assert on == off
     assert MXBLK not in on.values() and MX not in on.values()
     assert on[(2, 97)] == BATCHED and on[(4, 67)] == BATCHED and on[(2, 64)] == LDS2
+
+
+def test_eig_mx_0_after_an_earlier_query(pk, env):
+    """Every query reads the environment afresh: CLRSDP_EIG_MX=0 takes effect after multi-word
+    queries under the default in the same process, and unsetting it restores the default."""
+    assert pk.eigmin_kernel(64, 2) == MX and pk.eigmin_kernel(32, 4) == MX
+    env.setenv("CLRSDP_EIG_MX_BLK", "1")
+    assert pk.eigmin_kernel(97, 2) == MXBLK
+    env.setenv("CLRSDP_EIG_MX", "0")
+    assert pk.eigmin_kernel(64, 2) == LDS2 and pk.eigmin_kernel(32, 4) == LDS2
+    assert pk.eigmin_kernel(97, 2) == BATCHED
+    env.delenv("CLRSDP_EIG_MX")
+    assert pk.eigmin_kernel(64, 2) == MX and pk.eigmin_kernel(32, 4) == MX
+    assert pk.eigmin_kernel(97, 2) == MXBLK

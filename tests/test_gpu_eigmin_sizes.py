@@ -182,3 +182,25 @@ def test_eigmin_scaled_blocks_every_kernel(pk, words, n, ex):
     two of its largest leading-limb magnitude when they load it and multiply lambda_min back."""
     cases = [(f"spread{n}", "spread", n, ex), (f"decoupled{n}", "decoupled", n, ex)]
     _check(pk, words, cases, f"words={words} n={n} scale=2^{ex}")
+
+
+def test_eig_mx_0_takes_effect_inside_one_process(pk, monkeypatch):
+    """Two double-double blocks of n = 8, twice in one process.  With CLRSDP_EIG_MX unset the batch
+    takes eigmin_mx, which reports a route (0 certified, 1 flagged) for every block; with
+    CLRSDP_EIG_MX=0 the same call takes eigmin_lds2 for every block (route -1), although a
+    multi-word call has already run under the default.  lambda_min of the two calls agrees to
+    _tol(2, 8) of the block's spectral radius."""
+    refs = [_block("spread", 8, 60), _block("tiny", 8)]
+    blocks = [_for_words(r[0], 2) for r in refs]
+    monkeypatch.delenv("CLRSDP_EIG_MX", raising=False)
+    mx, routes_mx = pk.eigmin(blocks, precision_words=2, return_routes=True)
+    monkeypatch.setenv("CLRSDP_EIG_MX", "0")
+    lds2, routes_lds2 = pk.eigmin(blocks, precision_words=2, return_routes=True)
+    print(f"eigmin EIG_MX unset / 0: routes {list(routes_mx)} / {list(routes_lds2)}")
+    assert all(int(r) >= 0 for r in routes_mx), list(routes_mx)
+    assert all(int(r) == -1 for r in routes_lds2), list(routes_lds2)
+    with mpmath.workprec(320):
+        for (_, lam, rad), a, b in zip(refs, mx, lds2):
+            diff = abs(mpmath.mpf(a) - mpmath.mpf(b)) / rad
+            print(f"  |difference| / radius {float(diff):.3g} (tolerance {_tol(2, 8):.3g})")
+            assert diff <= _tol(2, 8), (float(diff), float(lam))

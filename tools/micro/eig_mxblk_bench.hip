@@ -73,17 +73,19 @@ void run(const char* name, int n, int nmat) {
   CK(hipMalloc(&out, 3 * nmat * sizeof(T)));
   CK(hipMemset(out, 0, 3 * nmat * sizeof(T)));
   CK(hipMemcpy(dA, h.data(), bytes, hipMemcpyHostToDevice));
-  auto build = [&](MatPlan<T>& p, const char* chain, const char* mx) {
-    if (chain) setenv("CLRSDP_EIG_BLK", chain, 1); else unsetenv("CLRSDP_EIG_BLK");
-    if (mx) setenv("CLRSDP_EIG_MX_BLK", mx, 1); else unsetenv("CLRSDP_EIG_MX_BLK");
+  // (the two switches as given here; every other one as the environment has it)
+  auto build = [&](MatPlan<T>& p, bool chain, bool mx) {
+    Switches sw = Switches::read();
+    sw.eig_blk = chain;
+    sw.eig_mx_blk = mx;
     for (int b = 0; b < nmat; ++b) p.add(dW + b * nn, n, n);
-    p.finalize(MatPlan<T>::Use::EIG_ONLY);
+    p.finalize(sw, MatPlan<T>::Use::EIG_ONLY);
   };
   MatPlan<T> pb, pc, pm;
-  build(pb, nullptr, nullptr);
-  build(pc, "1", nullptr);
-  build(pm, nullptr, "1");
-  if (MatPlan<T>::eig_dispatch(n, pm.eig_blk, pm.eig_mxblk) != CLRSDP_EIG_K_MXBLK) {
+  build(pb, false, false);
+  build(pc, true, false);
+  build(pm, false, true);
+  if (pm.eig_k != CLRSDP_EIG_K_MXBLK) {
     printf("%s n=%d: outside the route's range\n", name, n);
     return;
   }
